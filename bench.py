@@ -13,8 +13,9 @@ before this process touches the GPU); under torch.distributed.run each rank
 owns one GPU. Stripes shard across ranks as RowReaderOptions::range does
 (c++/src/Reader.cc:337-345): each rank decodes its own 10^8-row stripe, no
 collective in the timed region ("scaling": "weak"); value = all rows decoded
-/ max-over-ranks time. Outside the timed region the final row-batch concat
-is measured both ways SURVEY.md §8(e) names: every rank D2H's its rows into
+/ max-over-ranks time. With `--full` the final row-batch concat is measured
+outside the timed region, both ways SURVEY.md §8(e) names: every rank D2H's
+its rows into
 its own slice of one shared host batch (no collective), and an RCCL
 point-to-point gather of the device columns to rank 0 over xGMI.
 
@@ -24,9 +25,20 @@ generation the first ~100 launches run 5-7 % slow (scripts/ramp_probe.py,
 DESIGN.md §4). The JSON line reports them as `settle`; `--settle-ms 0` turns
 them off.
 
-The JSON line also carries
-  roofline     achieved algorithmic bytes (S + 8N per launch) / the kernel's
-               HIP-event duration on its own stream, vs 8 TB/s HBM3E peak;
+A plain run (`--gpus 1 --steps K --warmup W`) does what the headline figure
+needs and no more: generate and upload the stream, settle, warm up, time the
+K steps, print the JSON line. Its `roofline` comes from the HIP events around
+the same K launches: achieved algorithmic bytes (S + 8N per launch) / the
+kernel's duration on its own stream, vs 8 TB/s HBM3E peak.
+
+`--dump-outputs DIR` writes, after the timed steps, the column the last timed
+step decoded (see dump_outputs) so that two builds can be compared output for
+output: the inputs are seeded, the same arguments give the same stream.
+
+`--full` adds every other leg, each outside the timed region: the check of
+one decode against the generated values before the warm-up, the per-launch
+timestamps (`roofline.kernel_ms_timestamped`), the N > 1 concat legs, the
+copy-inclusive pipeline and
   cpu_baseline the reference's own C++ decoder as pyarrow bundles it (Apache
                ORC C++ 2.2.2, a build of c++/src) reading a C2-shaped file
                stripe by stripe on every usable core (value) and on 1 core;
@@ -196,6 +208,35 @@ def pyarrow_baseline(values, budget_s):
                               "rows_read": dn, "seconds": round(en, 2)}}
     finally:
         os.unlink(path)
+
+
+DUMP_SAMPLE = 2_000_000  # rows --dump-outputs keeps: three float64 arrays of them are 48 MB
+
+
+def dump_outputs(dirname, d_out, world, rank):
+    """--dump-outputs: the int64 column the last timed step left in HBM, as
+    float64 .npy files. A float64 holds 53 bits exactly, so each value is
+    stored as two exact halves: value = values_hi32 * 2^32 + values_lo32
+    (hi32 signed, lo32 unsigned). A column of more than DUMP_SAMPLE / world
+    rows is sampled at fixed rows (seed 0: its first and last 4096 rows and
+    uniform draws between them); rows.npy lists them. With N > 1 every rank
+    writes its own column under a rank<r>_ prefix."""
+    import torch
+
+    n = int(d_out.numel())
+    keep = max(1, DUMP_SAMPLE // world)
+    if n <= keep:
+        rows = np.arange(n, dtype=np.int64)
+    else:
+        edge = min(4096, keep // 4)
+        draws = np.random.default_rng(0).integers(0, n, size=keep - 2 * edge, dtype=np.int64)
+        rows = np.unique(np.concatenate([np.arange(edge), np.arange(n - edge, n), draws]))
+    got = d_out[torch.from_numpy(rows).to(d_out.device)].cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    tag = "rank%d_" % rank if world > 1 else ""
+    np.save(os.path.join(dirname, tag + "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, tag + "values_hi32.npy"), (got >> 32).astype(np.float64))
+    np.save(os.path.join(dirname, tag + "values_lo32.npy"), (got & 0xFFFFFFFF).astype(np.float64))
 
 
 def load_traffic():
@@ -450,6 +491,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the check of one decode, per-launch "
+                         "timestamps, concat legs (N > 1), the copy-inclusive pipeline, the CPU baselines; "
+                         "--no-verify, --no-concat, --copy-inclusive 0 and --no-cpu-baseline drop one each")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the column the last one decoded (a fixed sample of a "
+                         "large one) as float64 DIR/rows.npy, values_hi32.npy, values_lo32.npy")
     ap.add_argument("--rows", type=int, default=100_000_000)
     ap.add_argument("--stride", type=int, default=10_000)
     ap.add_argument("--cpu-budget", type=float, default=10.0)
@@ -472,6 +520,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="print each rank's RANK / LOCAL_RANK / WORLD_SIZE and exit before touching the GPU")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "c2":
+        ap.error("--dump-outputs writes the c2 column; the file workloads have no dump")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -522,10 +572,10 @@ def main():
     def step():
         orc_amd.decode_positions_device(ctx, d_src, d_pos, args.stride, N, True, d_out)
 
-    # verify one decode first (every value, compared on the device against the
+    # --full: verify one decode first (every value, compared on the device against the
     # generated values uploaded beforehand, so no host round trip leaves the
     # GPU idle between the check and the warm-up), then warm up
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         with torch.cuda.stream(stream):
             d_want = torch.from_numpy(values).to("cuda")
         stream.synchronize()
@@ -580,24 +630,28 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     kern_ms = e_start.elapsed_time(e_end) / args.steps
-    # outside the timed region: the same K launches with an event after each
-    # one (per-launch durations, as rocprofv3 --kernel-trace timestamps every
-    # dispatch): mean within ~1 % of the back-to-back figure, plus the spread
-    evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
-    evs[0].record(stream)
-    for i in range(args.steps):
-        step()
-        evs[i + 1].record(stream)
-    stream.synchronize()
-    ctx.synchronize()
-    per_launch = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_out, world, rank)
+    per_launch = None
+    if args.full:
+        # outside the timed region: the same K launches with an event after
+        # each one (per-launch durations, as a kernel trace timestamps every
+        # dispatch): mean within ~1 % of the back-to-back figure, plus the spread
+        evs = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+        evs[0].record(stream)
+        for i in range(args.steps):
+            step()
+            evs[i + 1].record(stream)
+        stream.synchronize()
+        ctx.synchronize()
+        per_launch = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
 
     concat = None
-    if dist and not args.no_concat:
+    if args.full and dist and not args.no_concat:
         concat = concat_legs(dist, d_out, N, world, rank, stream)
 
     copy_incl = None
-    if args.copy_inclusive and rank == 0:
+    if args.full and args.copy_inclusive and rank == 0:
         # host stream bytes (pinned) -> H2D -> decode -> D2H into a pinned
         # host column: the rate a host-memory caller sees,
         # serial (one stream) and pipelined (row-group chunks over an H2D, a
@@ -672,17 +726,18 @@ def main():
                 "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": traffic,
                 "kernel_ms": round(kern_ms, 4),
-                "kernel_ms_timestamped": {"mean": round(float(np.mean(per_launch)), 4),
-                                          "min": round(float(np.min(per_launch)), 4),
-                                          "max": round(float(np.max(per_launch)), 4)},
                 "algorithmic_bytes_per_launch": algo_bytes,
             },
         }
+        if per_launch:
+            line["roofline"]["kernel_ms_timestamped"] = {"mean": round(float(np.mean(per_launch)), 4),
+                                                         "min": round(float(np.min(per_launch)), 4),
+                                                         "max": round(float(np.max(per_launch)), 4)}
         if concat:
             line["concat"] = concat
         if copy_incl:
             line["copy_inclusive"] = copy_incl
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             port = cpu_baseline(data, N, args.cpu_budget)
             ref = pyarrow_baseline(values, args.cpu_budget)
             if ref is not None:

@@ -22,7 +22,7 @@ for s in $STEPS; do
     pytest) run pytest_gpu 1200 python -u -m pytest tests -m gpu -q -rf -x --timeout 120 --timeout-method thread ;;
     pytestcpu) run pytest_cpu 600 python -m pytest tests -m "not gpu" -q ;;
     smoke) run smoke 300 python __graft_entry__.py smoke ;;
-    bench) run bench 600 python bench.py ;;
+    bench) run bench 600 python bench.py --full ;;
     drift) run drift 300 python scripts/drift.py ;;
     ab) run ab 600 python scripts/ab_rlev2.py --variants 0,1,8,9 ;;
     ab13) run ab13 600 python scripts/ab_rlev2.py --bits 13 --variants 0,1,8,9 ;;
@@ -69,7 +69,7 @@ for s in $STEPS; do
     tfile) run tfile 900 python -u -m pytest ${TFILE_TESTS:-tests/test_gpu_reader.py} -m gpu -q -rf -x --timeout 120 --timeout-method thread ;;
     bench5)
       # the driver's settings (--steps 20 --warmup 5), variants interleaved
-      for v in ${B5_VARIANTS:-0 7 0 7}; do run bench5_v$v 300 python bench.py --steps 20 --warmup 5 --variant $v --no-cpu-baseline --copy-inclusive 0; cat $OUT/bench5_v$v.log >> $OUT/bench5_all.log; done ;;
+      for v in ${B5_VARIANTS:-0 7 0 7}; do run bench5_v$v 300 python bench.py --full --steps 20 --warmup 5 --variant $v --no-cpu-baseline --copy-inclusive 0; cat $OUT/bench5_v$v.log >> $OUT/bench5_all.log; done ;;
     ab64) run ab64 300 python scripts/ab_rlev2.py --data random --bits 64 --variants ${AB_VARIANTS:-0,2,7,20} --rounds 5 --refs copy,probe5 ;;
     bf) for w in ${BF_WORKLOADS:-c5 c4 c3}; do run bf_$w 600 python scripts/bench_file.py --workload $w --row-reader ${BF_ARGS:-}; done ;;
     proffile)
@@ -77,7 +77,7 @@ for s in $STEPS; do
       for w in ${PF_WORKLOADS:-c5}; do run prof_$w 600 rocprofv3 --kernel-trace --stats -d "$PWD/$OUT/prof_$w" -o run --output-format csv -- python3 scripts/bench_file.py --workload $w --iters 1 --no-cpu-baseline; done ;;
     dbg11) run dbg11 300 python scripts/dbg_file11.py ;;
     treader) run treader 600 python -u -m pytest tests/test_gpu_reader.py -m gpu -q -rf -x --timeout 120 --timeout-method thread ;;
-    benchwalk) run bench_walk 600 python bench.py --variant 1 --no-cpu-baseline ;;
+    benchwalk) run bench_walk 600 python bench.py --full --variant 1 --no-cpu-baseline ;;
     prof)
       export TMPDIR=/tmp
       run prof 600 rocprofv3 --kernel-trace --stats -d "$PWD/$OUT/prof" -o run --output-format csv -- python3 bench.py --steps 50 --warmup 100 --no-cpu-baseline --no-verify --copy-inclusive 0 ;;

@@ -157,7 +157,7 @@ def test_bench_two_ranks_on_one_gpu_with_gloo():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-                          "--rows", "2000000", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
+                          "--full", "--rows", "2000000", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
                           "--copy-inclusive", "0"], capture_output=True, text=True, timeout=240, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
