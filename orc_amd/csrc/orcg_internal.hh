@@ -199,7 +199,7 @@ void warm_rlev2_expand(hipStream_t s);
 
 // RLEv2 kernel variants a context accepts (orcg_rlev2_variants): 0 default,
 // 1 wave-walk, and pins of single tiled instances (launch_rlev2_tiled).
-constexpr int kMaxRlev2Variant = 8;
+constexpr int kMaxRlev2Variant = 9;
 bool rlev2_variant_valid(int v);
 // d_count (may be null): the value count on the device, nvalues then
 // bounds the output only.

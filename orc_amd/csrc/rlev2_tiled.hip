@@ -86,6 +86,9 @@ constexpr uint32_t kVparMin = ORCG_VPAR_MIN;
 #define ORCG_VPAR_FRAG 2
 #endif
 constexpr uint32_t kVparFrag = ORCG_VPAR_FRAG;  // short-run groups per 64 runs before all go value-parallel
+#ifndef ORCG_FLAT_RUNS  // flat DIRECT path (kOptFlat): runs in flight per wave, 1 or 2
+#define ORCG_FLAT_RUNS 2
+#endif
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kDpErr = 0x80000000u;     // DP entry: a corrupt run starts here
 constexpr uint16_t kSink = 0xffffu;          // chain successor: none
@@ -124,6 +127,9 @@ constexpr int kOptGrpT = 8192;      // serial groups of short runs (one lane per
                                     // temporal stores, so L2 merges the partial lines before they reach HBM
 constexpr int kOptTable = 16384;    // two-pass (RunTab): dense passes write their runs to the run table for
                                     // rlev2_expand_kernel instead of expanding them
+constexpr int kOptFlat = 32768;     // a segment's leading chain of equal full DIRECT runs of >= 40 bits (int64
+                                    // output): one header probe, then expanded straight from memory (flat_*),
+                                    // no LDS window, no walk, no barrier
 
 // Debug build only (ORCG_AB_FLAGS=-DORCG_DEBUG_COVER): every expansion path
 // counts the values of the runs it expands; each pass checks the count
@@ -517,6 +523,83 @@ __device__ __forceinline__ void fill(uint32_t* win, __amdgpu_buffer_rsrc_t rs, u
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)((char*)win + off),
                                              16, wrel + off + lane * 16, 0, 0,
                                              (kOpt & kOptNTLoad) ? 2 : 0);
+}
+
+// The flat DIRECT path (kOptFlat). A writer emits a wide random column as
+// back-to-back DIRECT runs of 512 values at one width: every such run has the
+// same two header bytes and the same byte length B = 2 + 512 * nb (nb = W / 8
+// bytes per value), and a run's extent depends on its own header only. So if
+// the header at pos + k * B equals the one at pos for k = 1 .. m - 1, those m
+// runs start exactly there (by induction): one memory round trip validates
+// the chain, and each lane then loads its values' bytes straight from memory,
+// as a flat copy does. Every wave probes for itself (the same few cache
+// lines), so the path needs no LDS, no barrier and no walk.
+//
+// flat_probe: lane k reads the two bytes at descriptor offset prel + k * B,
+// for the B of each of the four widths (40, 48, 56, 64 bits) at once; the
+// first header then picks the width, so the probe is a single round trip.
+// Only lanes k < kmax whose run would end at or before descriptor offset
+// `lim` take part; the others hold zeros, which is no eligible header.
+// Returns m, the number of leading runs whose header equals the first one
+// (not the number of matches: the chain ends at the first mismatch), 0 when
+// the first run is not eligible: DIRECT, 512 values, W >= 40.
+__device__ __forceinline__ uint32_t flat_probe(__amdgpu_buffer_rsrc_t rs, uint32_t prel, uint32_t lim,
+                                               uint32_t kmax, int lane, uint32_t* nb) {
+  uint32_t h[4];
+#pragma unroll
+  for (uint32_t wi = 0; wi < 4; ++wi) {
+    const uint32_t B = 2u + 512u * (5u + wi);
+    const uint64_t off = (uint64_t)prel + (uint32_t)lane * B;
+    uint32_t x = 0;
+    if ((uint32_t)lane < kmax && off + B <= lim) {
+      // the aligned-down dword pair around the two bytes
+      const auto q = __builtin_amdgcn_raw_buffer_load_b64(rs, (uint32_t)off & ~3u, 0, 0);
+      const uint64_t qq = ((uint64_t)q[1] << 32) | q[0];
+      x = (uint32_t)(qq >> (((uint32_t)off & 3u) * 8u)) & 0xffffu;
+    }
+    h[wi] = x;
+  }
+  const uint32_t hdr = uni(h[0]);  // lane 0: the first header, whatever the width
+  // 01 wwwww 1 | 11111111: DIRECT, L - 1 = 0x1ff, width code 28 .. 31
+  if ((hdr & 0xfff9u) != 0xff79u) return 0;
+  const uint32_t wi = (hdr >> 1) & 3u;
+  const uint32_t mine = wi == 0 ? h[0] : (wi == 1 ? h[1] : (wi == 2 ? h[2] : h[3]));
+  const uint64_t differ = ~__ballot(mine == hdr);
+  *nb = 5u + wi;
+  return differ ? (uint32_t)__builtin_ctzll(differ) : 64u;
+}
+
+// flat_expand: kRuns full runs of 512 values of nb bytes each with one wave,
+// run q's packed data at descriptor offset d + q * dstep, its values at
+// out + q * ostep. Each lane loads the three dwords at the aligned-down
+// address of its value (expand_run's extract, from memory instead of LDS);
+// all of the loads are issued before the first store.
+template <int kOpt, int kRuns, typename T>
+__device__ __forceinline__ void flat_expand(__amdgpu_buffer_rsrc_t rs, uint32_t d, uint32_t dstep, uint32_t nb,
+                                            int is_signed, T* out, uint32_t ostep, int lane) {
+  u32x3 w[kRuns][kMaxRunUnroll];
+#pragma unroll
+  for (int q = 0; q < kRuns; ++q) {
+#pragma unroll
+    for (int it = 0; it < kMaxRunUnroll; ++it) {
+      const uint32_t rel = d + (uint32_t)q * dstep + (uint32_t)(it * kWave + lane) * nb;
+      const auto t = __builtin_amdgcn_raw_buffer_load_b96(rs, rel & ~3u, 0, 2);
+      w[q][it].x = t[0];
+      w[q][it].y = t[1];
+      w[q][it].z = t[2];
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < kRuns; ++q) {
+#pragma unroll
+    for (int it = 0; it < kMaxRunUnroll; ++it) {
+      const uint32_t j = (uint32_t)(it * kWave + lane);
+      const uint32_t rel = d + (uint32_t)q * dstep + j * nb;
+      uint64_t v = field(w[q][it], rel, 0, 8u * nb);
+      if (is_signed) v = unzigzag(v);
+      store1<kOpt>(out + (uint32_t)q * ostep + j, v);
+    }
+  }
 }
 
 struct WalkResult {
@@ -1621,6 +1704,58 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
   uint32_t sync_par = 0;
   if (tid < 4) s_sync[tid >> 1][tid & 1] = 0;  // ordered before use by the first window's barrier
   PROF_DECL;
+  if constexpr ((kOpt & kOptFlat) != 0 && sizeof(T) == 8 && !kPipe && kDense == 0 && kDefer == 0) {
+    // The flat prologue (flat_probe / flat_expand above): the segment's
+    // leading chain of equal full DIRECT runs of >= 40 bits, taken only while
+    // the runs lie wholly inside the requested values and end at or before
+    // the segment's end. Whatever comes next (another header, a shorter or
+    // narrower run, another kind, a partial or truncated run, a run that
+    // straddles the segment's end) is left to the window loop below with
+    // the advanced pos / vi, with its checks and reports as they are; a
+    // segment that has gone there stays there.
+    if (!queued) {
+      // no flat run ends past the segment, nor closer than 4 bytes to the
+      // descriptor's end (a value's 12-byte extract reads up to 4 bytes past it)
+      const uint64_t flat_end = seg_end < bias + nrec - 4u ? seg_end : bias + nrec - 4u;
+      const uint64_t vstop = v_next < value_end ? v_next : value_end;
+      const uint32_t wv = uni((uint32_t)wave);
+      // runs in flight per wave (ORCG_AB_FLAGS=-DORCG_FLAT_RUNS=1 for the
+      // A/B): two measured 1 % faster than one on C2
+      constexpr int kRuns = ORCG_FLAT_RUNS;
+      static_assert(kRuns == 1 || kRuns == 2, "flat runs in flight");
+      uint32_t flat_runs = 0;
+      while (vi >= value_begin && vi < vstop && pos < flat_end) {
+        const uint64_t kv = (vstop - vi) / 512u;  // whole runs before the next segment's / the last value
+        uint32_t nb = 0;
+        const uint32_t m = flat_probe(rs, (uint32_t)(pos - bias), (uint32_t)(flat_end - bias),
+                                      kv < 64u ? (uint32_t)kv : 64u, lane, &nb);
+        if (m == 0) break;
+        const uint32_t B = 2u + 512u * nb;
+        const uint32_t d0 = (uint32_t)(pos - bias) + 2u;
+        T* const out = dst + (vi - value_begin);
+        // wave w takes runs w, w + 4, ...
+        for (uint32_t r = wv; r < m; r += kWaves * kRuns) {
+          if constexpr (kRuns == 2) {
+            if (r + kWaves < m) {
+              flat_expand<kOpt, 2>(rs, d0 + r * B, kWaves * B, nb, is_signed, out + 512u * r, kWaves * 512u, lane);
+              continue;
+            }
+          }
+          flat_expand<kOpt, 1>(rs, d0 + r * B, 0, nb, is_signed, out + 512u * r, 0, lane);
+        }
+        pos += (uint64_t)m * B;
+        vi += 512ull * m;
+        flat_runs += m;
+        if (m < 64u) break;  // the chain ended; 64 runs: there may be more, probe again
+      }
+      PROF_MARK(7);
+#ifdef ORCG_PHASE_PROF
+      if (tid == 0) atomicAdd(&g_phase[10], (unsigned long long)flat_runs);  // runs expanded flat
+#else
+      (void)flat_runs;
+#endif
+    }
+  }
   if constexpr (!kPipe) {
     uint64_t pwpos = ~0ull;  // previous window (stream offset) and its valid bytes
     uint32_t pneed = 0;
@@ -2045,11 +2180,12 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
 }  // namespace
 
 // Variants (ctx->rlev2_variant, include/orcg.h): 0 = the density-adaptive
-// default; 2-8 pin one instance (the parity tests run each: 6 = the union
+// default; 2-9 pin one instance (the parity tests run each: 6 = the union
 // instance in two passes, the default's below 1.25 B/value; 8 = the same in
-// one pass); 1 = the wave-walk kernel (rlev2_kernels.hip). (The round 1-5
+// one pass; 9 = instance 2 without the flat DIRECT path, its in-binary A/B
+// control); 1 = the wave-walk kernel (rlev2_kernels.hip). (The round 1-5
 // tuning instances of the A/B sweeps were removed in round 6.)
-bool rlev2_variant_valid(int v) { return v >= 0 && v <= 8; }
+bool rlev2_variant_valid(int v) { return v >= 0 && v <= 9; }
 
 static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
   // {stamp, byte offset, value index} per launch-wide segment, stamps zeroed
@@ -2077,6 +2213,8 @@ static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
 //  * >= 5 B/value (wide values, W >= 40): 33 KB windows (4 WG/CU) filled
 //    through registers, one walking wave, no queue (writers emit wide random
 //    values in long DIRECT runs; the empty queue drain cost 4 us of C2's 290);
+//    a segment's leading chain of equal full DIRECT runs skips the windows
+//    altogether (kOptFlat);
 //  * 1.25 - 5 B/value: 21 KB serial windows (6 WG/CU), queueing segments whose
 //    first runs are short by values for the dense drain (long DIRECT / DELTA /
 //    PATCHED_BASE runs of 10-40-bit values: 5.3-6.1 TB/s; short runs of wide
@@ -2284,7 +2422,8 @@ static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t sr
 
   const unsigned grid_s = (unsigned)nsegs;
   switch (variant) {
-    case 2: ORCG_KX(kWide | kOptD3, 33, false, 1, 0, 0, grid_s); break;  // 33 KB register-filled serial, no queue
+    case 2: ORCG_KX(kWide | kOptD3 | kOptFlat, 33, false, 1, 0, 0, grid_s); break;  // 33 KB register-filled serial, no
+                                                                                    // queue, flat DIRECT prologue
     case 3: ORCG_DEFERRING(kSer | kOptD3, 21, 6, kSer | kOptD3); break;   // 21 KB serial + dense drain
     case 4: ORCG_KX(kSer | kOptD3, 8, false, 6, 2, 0, grid_s); break;   // dense v3, 8.5 KB
     case 5: ORCG_KX(kSer | kOptD3, 12, false, 5, 2, 0, grid_s); break;  // dense v3, 12.5 KB
@@ -2299,6 +2438,7 @@ static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t sr
     }
     case 7: ORCG_DEFERRING(kWide | kOptD3, 33, 1, kSer | kOptD3); break;  // 33 KB serial + dense drain (round-3 default, A/B)
     case 8: ORCG_KX(kSer | kOptD3 | kOptUnion, 8, false, 6, 2, 0, grid_s); break;  // union in one pass (round-5 default)
+    case 9: ORCG_KX(kWide | kOptD3, 33, false, 1, 0, 0, grid_s); break;  // 2 without the flat prologue (A/B control)
     default: return set_error(ctx, ORCG_INVALID_ARGUMENT, "unknown RLEv2 kernel variant");
   }
 #undef ORCG_DEFERRING
@@ -2368,7 +2508,7 @@ int stage_table(Ctx* ctx, const void* src, size_t bytes, const void** out) {
   return hip_check(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream), "H2D jobs");
 }
 
-bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 8); }
+bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 9); }
 
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out) {
   const int pinned = ctx->rlev2_variant;
@@ -2382,19 +2522,19 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     return ORCG_OK;
   }
   // one launch per instance: group the streams by the instance they get
-  std::vector<RleJob> group[9];
+  std::vector<RleJob> group[10];
   for (uint32_t j = 0; j < njobs; ++j) {
     const RleJob& J = jobs[j];
     if (J.nsegs == 0 || J.nvalues == 0) continue;
     group[pinned ? pinned : default_variant(J.src_len, J.nvalues)].push_back(J);
   }
   if (debug_on("jobs"))
-    for (int v = 2; v <= 8; ++v)
+    for (int v = 2; v <= 9; ++v)
       for (const RleJob& J : group[v])
         fprintf(stderr, "rle job: instance %d bytes %llu values %llu segments %llu (%.3f B/value)\n", v,
                 (unsigned long long)J.src_len, (unsigned long long)J.nvalues, (unsigned long long)J.nsegs,
                 (double)J.src_len / (double)J.nvalues);
-  for (int v = 2; v <= 8; ++v) {
+  for (int v = 2; v <= 9; ++v) {
     std::vector<RleJob>& g = group[v];
     if (g.empty()) continue;
     // workgroups start in index order: the streams with the most stream

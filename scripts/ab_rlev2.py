@@ -105,7 +105,8 @@ def main():
         ms = float(np.median(ts))
         byts = 16 * n if isinstance(var, str) else S + 8 * n
         print(json.dumps({"variant": var, "bits": args.bits, "data": args.data, "stream_B_per_value": round(S / n, 3), "ms_median": round(ms, 4),
-                          "ms_min": round(float(np.min(ts)), 4),
+                          "ms_min": round(float(np.min(ts)), 4), "ms_max": round(float(np.max(ts)), 4),
+                          "ms_rounds": [round(float(t), 4) for t in ts],
                           "GBps": round(byts / ms / 1e6, 1), "bytes": int(byts)}), flush=True)
     if set(bad) - keep:
         sys.exit(3)

@@ -19,7 +19,9 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 os.environ.setdefault("ORCG_LIB", "liborcgpu_prof.so")
 
-PHASES = ["fill", "serial_walk", "serial_expand", "dense_dp", "dense_chain", "dense_emit", "dense_expand"]
+PHASES = ["fill", "serial_walk", "serial_expand", "dense_dp", "dense_chain", "dense_emit", "dense_expand", "flat"]
+# event counters behind the phase ticks (g_phase[8..10]), per launch
+COUNTS = {"runs_walked": 8, "serial_passes": 9, "runs_flat": 10}
 
 
 def main():
@@ -66,8 +68,9 @@ def main():
         L.orcg_debug_phase_counters(buf, 16, 1)
         ticks = np.array(buf[: len(PHASES)], dtype=np.float64) / args.iters
         tot = ticks.sum()
+        counts = {k: int(buf[i]) // args.iters for k, i in COUNTS.items()}
         print(json.dumps({"variant": var, "data": args.data, "bits": args.bits, "rows": n,
-                          "stream_B_per_value": round(data.size / n, 3), "ms": round(ms, 4),
+                          "stream_B_per_value": round(data.size / n, 3), "ms": round(ms, 4), **counts,
                           "wg_us_per_launch": {p: round(t / 100.0, 1) for p, t in zip(PHASES, ticks)},
                           "share": {p: round(t / tot, 3) for p, t in zip(PHASES, ticks) if tot}}), flush=True)
 
