@@ -39,12 +39,95 @@ def type_msg(kind, subtypes=(), names=()):
     return m
 
 
-def orc_file(body, stripes, types, num_rows, footer_length_override=None):
+def orc_file(body, stripes, types, num_rows, footer_length_override=None, row_index_stride=None):
     """'ORC' + body + Footer + PostScript + 1-byte PostScript length
-    (uncompressed)."""
+    (uncompressed). row_index_stride: Footer.rowIndexStride (field 8), left
+    out when None."""
     footer = b"".join(field_bytes(3, s) for s in stripes)
     footer += b"".join(field_bytes(4, t) for t in types)
     footer += field_varint(6, num_rows)
+    if row_index_stride is not None:
+        footer += field_varint(8, row_index_stride)
     flen = len(footer) if footer_length_override is None else footer_length_override
     ps = field_varint(1, flen) + field_varint(2, 0) + field_bytes(4, varint(0) + varint(12)) + field_bytes(8000, b"ORC")
     return b"ORC" + body + footer + ps + bytes([len(ps)])
+
+
+# ---- whole files: an uncompressed struct of non-nullable columns ------------
+# Stream.Kind, ColumnEncoding.Kind and Type.Kind numbers (ORCv1.md "Stripe
+# Footer", "Type Information")
+PRESENT, DATA, LENGTH, DICTIONARY_DATA, SECONDARY, ROW_INDEX = 0, 1, 2, 3, 5, 6
+ENC_DIRECT, ENC_DICTIONARY, ENC_DIRECT_V2, ENC_DICTIONARY_V2 = 0, 1, 2, 3
+T_SHORT, T_INT, T_LONG, T_STRING, T_STRUCT = 2, 3, 4, 7, 12
+
+
+def stream_msg(kind, column, length):
+    return field_varint(1, kind) + field_varint(2, column) + field_varint(3, length)
+
+
+def encoding_msg(kind, dictionary_size=None):
+    return field_varint(1, kind) + (b"" if dictionary_size is None else field_varint(2, dictionary_size))
+
+
+def row_index_msg(entries):
+    """RowIndex{ repeated RowIndexEntry entry = 1 { repeated uint64 positions
+    = 1 [packed] } }: entries = one list of positions per row group (an empty
+    list gives an entry without positions, as the root struct has)."""
+    out = b""
+    for e in entries:
+        out += field_bytes(1, field_bytes(1, b"".join(varint(p) for p in e)) if len(e) else b"")
+    return out
+
+
+class CraftColumn:
+    """One column of one stripe: its streams [(Stream.Kind, bytes)] in file
+    order, its ColumnEncoding, and (for a row index) its positions, one list
+    per row group in the order the readers consume them (ORCv1.md "Indexes":
+    uncompressed integer stream: byte offset of the run, values to skip in
+    it; a dictionary string column: the pair of DATA; a direct string column:
+    the DATA byte offset, then the pair of LENGTH)."""
+
+    def __init__(self, streams, positions=None, encoding=ENC_DIRECT_V2, dictionary_size=None):
+        self.streams = [(k, bytes(b)) for k, b in streams]
+        self.positions = positions
+        self.encoding = encoding
+        self.dictionary_size = dictionary_size
+
+
+def struct_stripe(columns, row_index=True):
+    """(index section, data section, stripe footer) of a stripe whose root
+    struct (column 0, no streams, DIRECT) has `columns` (CraftColumn, ids 1..)
+    as children, none with a PRESENT stream. With row_index, the index section
+    holds one ROW_INDEX stream per column, the root's with empty entries."""
+    index, data, sf = b"", b"", b""
+    if row_index:
+        groups = len(columns[0].positions)
+        for cid, c in enumerate([None] + list(columns)):
+            entries = [[]] * groups if c is None else [[int(p) for p in e] for e in c.positions]
+            assert len(entries) == groups
+            m = row_index_msg(entries)
+            index += m
+            sf += field_bytes(1, stream_msg(ROW_INDEX, cid, len(m)))
+    for cid, c in enumerate(columns, start=1):
+        for kind, b in c.streams:
+            data += b
+            sf += field_bytes(1, stream_msg(kind, cid, len(b)))
+    sf += field_bytes(2, encoding_msg(ENC_DIRECT))
+    for c in columns:
+        sf += field_bytes(2, encoding_msg(c.encoding, c.dictionary_size))
+    return index, data, sf
+
+
+def struct_file(names, kinds, stripes, row_index_stride):
+    """An uncompressed file of struct<names[i]: kinds[i]> (Type.Kind numbers)
+    with any number of stripes = [(num_rows, [CraftColumn per column])]. A
+    row_index_stride of 0 writes no index section."""
+    body, infos, total = b"", [], 0
+    for num_rows, columns in stripes:
+        assert len(columns) == len(names)
+        index, data, sf = struct_stripe(columns, row_index=row_index_stride > 0)
+        infos.append(stripe_info(3 + len(body), len(index), len(data), len(sf), num_rows))
+        body += index + data + sf
+        total += num_rows
+    types = [type_msg(T_STRUCT, list(range(1, len(names) + 1)), names)] + [type_msg(k) for k in kinds]
+    return orc_file(body, infos, types, total, row_index_stride=row_index_stride)
