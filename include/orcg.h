@@ -80,11 +80,13 @@ enum { ORCG_RLEV2_TILED = 0, ORCG_RLEV2_WAVE_WALK = 1 };
 /* Other accepted values pin one instance of the tiled kernel (used by the
  * parity tests to cover every instance the default may pick, and by A/B
  * timing); orcg_rlev2_variants lists them: 2 = 33 KB register-filled serial
- * windows with the flat DIRECT prologue (the default's for >= 5 stream bytes
- * per value), 3 = 21 KB serial windows + dense drain, 4 / 5 = dense 8.5 /
+ * windows with the flat DIRECT prologue, W=64 runs in aligned 16-byte chunks
+ * (the default's for >= 5 stream bytes per value), 3 = 21 KB serial windows + dense drain, 4 / 5 = dense 8.5 /
  * 12.5 KB, 6 = the union instance in two passes, 7 = 33 KB serial + dense
  * drain, 8 = the union instance in one pass, 9 = 2 without the flat DIRECT
- * prologue (its A/B control). Unknown values: INVALID_ARGUMENT. */
+ * prologue (its A/B control), 10 = 2 with the prologue's 8-byte accesses at
+ * every width (the A/B control of the 16-byte chunks). Unknown values:
+ * INVALID_ARGUMENT. */
 int orcg_ctx_set_rlev2_variant(orcg_ctx* ctx, int variant);
 /* Writes up to `cap` accepted variant ids to `out`; returns how many exist. */
 int orcg_rlev2_variants(int* out, int cap);

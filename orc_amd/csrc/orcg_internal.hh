@@ -198,8 +198,15 @@ int launch_rlev2_expand(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is
 void warm_rlev2_expand(hipStream_t s);
 
 // RLEv2 kernel variants a context accepts (orcg_rlev2_variants): 0 default,
-// 1 wave-walk, and pins of single tiled instances (launch_rlev2_tiled).
-constexpr int kMaxRlev2Variant = 9;
+// 1 wave-walk, and pins of single tiled instances (launch_rlev2_tiled): 2-8
+// the default's instances and their one-pass / drain forms, 9 = 2 without the
+// flat DIRECT prologue, 10 = 2 with the prologue's 8-byte form at every width
+// (no 16-byte chunks for W=64). An ORCG_FLAT16_STEPS build (A/B) adds 11-14.
+#ifdef ORCG_FLAT16_STEPS
+constexpr int kMaxRlev2Variant = 14;
+#else
+constexpr int kMaxRlev2Variant = 10;
+#endif
 bool rlev2_variant_valid(int v);
 // d_count (may be null): the value count on the device, nvalues then
 // bounds the output only.

@@ -89,6 +89,17 @@ constexpr uint32_t kVparFrag = ORCG_VPAR_FRAG;  // short-run groups per 64 runs 
 #ifndef ORCG_FLAT_RUNS  // flat DIRECT path (kOptFlat): runs in flight per wave, 1 or 2
 #define ORCG_FLAT_RUNS 2
 #endif
+// its 16-byte form for W=64 runs (kOptFlat16): runs in flight per wave, 2, 3
+// or 5 (a wave's share of a 10,000-row segment: measured 1.1 % faster than 2 on
+// C2, 3 within noise of 2), and whether a value pair is one 16-byte store when
+// the output is 16-byte aligned (measured 0.8 % slower than two 8-byte stores:
+// off). DESIGN.md §4.
+#ifndef ORCG_FLAT16_RUNS
+#define ORCG_FLAT16_RUNS 5
+#endif
+#ifndef ORCG_FLAT16_STORE16
+#define ORCG_FLAT16_STORE16 0
+#endif
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kDpErr = 0x80000000u;     // DP entry: a corrupt run starts here
 constexpr uint16_t kSink = 0xffffu;          // chain successor: none
@@ -130,6 +141,12 @@ constexpr int kOptTable = 16384;    // two-pass (RunTab): dense passes write the
 constexpr int kOptFlat = 32768;     // a segment's leading chain of equal full DIRECT runs of >= 40 bits (int64
                                     // output): one header probe, then expanded straight from memory (flat_*),
                                     // no LDS window, no walk, no barrier
+constexpr int kOptFlat16 = 65536;   // kOptFlat's W=64 runs: aligned 16-byte chunk loads shifted in registers, two
+                                    // values per lane, ORCG_FLAT16_RUNS runs in flight (flat_expand16)
+// A/B steps of kOptFlat16 (variants 11-14 of an ORCG_FLAT16_STEPS build only):
+// runs in flight other than ORCG_FLAT16_RUNS, 8-byte stores
+constexpr int kOptF16Runs2 = 1 << 17, kOptF16Runs3 = 1 << 18, kOptF16Runs5 = 1 << 19, kOptF16St8 = 1 << 20,
+              kOptF16St16 = 1 << 21;
 
 // Debug build only (ORCG_AB_FLAGS=-DORCG_DEBUG_COVER): every expansion path
 // counts the values of the runs it expands; each pass checks the count
@@ -539,19 +556,20 @@ __device__ __forceinline__ void fill(uint32_t* win, __amdgpu_buffer_rsrc_t rs, u
 // for the B of each of the four widths (40, 48, 56, 64 bits) at once; the
 // first header then picks the width, so the probe is a single round trip.
 // Only lanes k < kmax whose run would end at or before descriptor offset
-// `lim` take part; the others hold zeros, which is no eligible header.
+// `lim` (W=64 runs: `lim64`, the 16-byte form's reach) take part; the others
+// hold zeros, which is no eligible header.
 // Returns m, the number of leading runs whose header equals the first one
 // (not the number of matches: the chain ends at the first mismatch), 0 when
 // the first run is not eligible: DIRECT, 512 values, W >= 40.
 __device__ __forceinline__ uint32_t flat_probe(__amdgpu_buffer_rsrc_t rs, uint32_t prel, uint32_t lim,
-                                               uint32_t kmax, int lane, uint32_t* nb) {
+                                               uint32_t lim64, uint32_t kmax, int lane, uint32_t* nb) {
   uint32_t h[4];
 #pragma unroll
   for (uint32_t wi = 0; wi < 4; ++wi) {
     const uint32_t B = 2u + 512u * (5u + wi);
     const uint64_t off = (uint64_t)prel + (uint32_t)lane * B;
     uint32_t x = 0;
-    if ((uint32_t)lane < kmax && off + B <= lim) {
+    if ((uint32_t)lane < kmax && off + B <= (wi == 3 ? lim64 : lim)) {
       // the aligned-down dword pair around the two bytes
       const auto q = __builtin_amdgcn_raw_buffer_load_b64(rs, (uint32_t)off & ~3u, 0, 0);
       const uint64_t qq = ((uint64_t)q[1] << 32) | q[0];
@@ -598,6 +616,98 @@ __device__ __forceinline__ void flat_expand(__amdgpu_buffer_rsrc_t rs, uint32_t 
       uint64_t v = field(w[q][it], rel, 0, 8u * nb);
       if (is_signed) v = unzigzag(v);
       store1<kOpt>(out + (uint32_t)q * ostep + j, v);
+    }
+  }
+}
+
+// flat_expand16 (kOptFlat16): flat_expand for W=64 runs, two values per lane.
+// A run's payload starts at descriptor offset d = a + s, a = d & ~15: the
+// shift s (0-15) is the same for the whole run, so the wave loads the payload
+// as aligned 16-byte chunks (chunk it * 64 + lane in iteration it, 0-3, and
+// chunk 256 one dword per lane: lane e0 + k holds its dword k) and lane l's value pair 2 * (it * 64 + l) is bytes
+// [s, s + 16) of its own chunk followed by its right neighbour's: the
+// neighbour's dwords come by a one-lane DPP shift (lane 63 takes lane 0 of
+// the next iteration's chunk, or chunk 256), the dword offset s >> 2 picks
+// the code (flat16_run<K>, a wave-uniform branch), v_alignbyte shifts by
+// s & 3. The chunks reach up to 15 bytes past the payload (chunk 256 is
+// loaded whatever s is) and their addresses are not left to the descriptor's
+// range check (the run's start is the scalar offset): the caller takes a run this way only if it ends 16
+// bytes or more before the descriptor's end. cnt <= kRuns runs (q-th at
+// d + q * dstep, values at out + q * ostep), all loads before the first
+// store; a pair is two 8-byte stores, or (kSt16) one 16-byte store when `out`
+// is 16-byte aligned (ostep is even).
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+// lane i takes lane i + 1's x (wave_shl:1), lane 63 takes `last`
+__device__ __forceinline__ uint32_t next_lane(uint32_t x, uint32_t last) {
+  return (uint32_t)__builtin_amdgcn_update_dpp((int)last, (int)x, 0x130, 0xf, 0xf, false);
+}
+
+template <int kOpt, int K>
+__device__ __forceinline__ void flat16_run(const u32x4 (&c)[4], uint32_t e, int e0, uint32_t r, int is_signed,
+                                           bool st16, int64_t* out, int lane) {
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    uint32_t D[8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) D[k] = c[it][k];
+#pragma unroll
+    for (int k = 0; k <= K; ++k) D[4 + k] = next_lane(c[it][k], it < 3 ? uni(c[it < 3 ? it + 1 : 3][k]) : rdlane(e, e0 + k));
+    uint64_t v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const uint32_t lo = __builtin_amdgcn_alignbyte(D[K + 2 * h + 1], D[K + 2 * h], r);
+      const uint32_t hi = __builtin_amdgcn_alignbyte(D[K + 2 * h + 2], D[K + 2 * h + 1], r);
+      v[h] = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
+      if (is_signed) v[h] = unzigzag(v[h]);
+    }
+    // the lane's 16 bytes + a constant: the loads' vector offset serves the stores too
+    int64_t* const o = (int64_t*)((char*)out + 16u * (uint32_t)lane) + 2 * kWave * it;
+    if (st16) {
+      store2<kOpt>(o, v[0], v[1]);
+    } else {
+      store1<kOpt>(o, v[0]);
+      store1<kOpt>(o + 1, v[1]);
+    }
+  }
+}
+
+template <int kOpt, int kRuns, bool kSt16>
+__device__ __forceinline__ void flat_expand16(__amdgpu_buffer_rsrc_t rs, uint32_t d, uint32_t dstep, uint32_t cnt,
+                                              int is_signed, int64_t* out, uint32_t ostep, int lane) {
+  cnt = uni(cnt);
+  d = uni(d);
+  u32x4 c[kRuns][4];
+  // the chunks' addresses: the lane's 16 bytes as the vector offset, the
+  // run's (wave-uniform) aligned start as the scalar one
+  const uint32_t l16 = 16u * (uint32_t)lane;
+#pragma unroll
+  for (int q = 0; q < kRuns; ++q) {
+    if ((uint32_t)q < cnt) {
+      const uint32_t a = (d + (uint32_t)q * dstep) & ~15u;
+#pragma unroll
+      for (int it = 0; it < 4; ++it)
+        c[q][it] = __builtin_amdgcn_raw_buffer_load_b128(rs, l16, a + 1024u * (uint32_t)it, 2);
+    }
+  }
+  // chunk 256 of every run in one register: lane 4 * q + k holds dword k of
+  // run q's (the lanes past the last run load the last run's again)
+  static_assert(4 * kRuns <= kWave, "one lane per dword of the runs' last chunks");
+  const uint32_t eq = (uint32_t)lane >> 2 < cnt ? (uint32_t)lane >> 2 : cnt - 1u;
+  const uint32_t e =
+      __builtin_amdgcn_raw_buffer_load_b32(rs, ((d + eq * dstep) & ~15u) + 4096u + 4u * ((uint32_t)lane & 3u), 0, 2);
+  const bool st16 = kSt16 && uni((uint32_t)(uintptr_t)out & 15u) == 0;
+#pragma unroll
+  for (int q = 0; q < kRuns; ++q) {
+    if ((uint32_t)q < cnt) {
+      const uint32_t s = (d + (uint32_t)q * dstep) & 15u;
+      int64_t* const o = out + (uint32_t)q * ostep;
+      switch (s >> 2) {
+        case 0: flat16_run<kOpt, 0>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
+        case 1: flat16_run<kOpt, 1>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
+        case 2: flat16_run<kOpt, 2>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
+        default: flat16_run<kOpt, 3>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
+      }
     }
   }
 }
@@ -1724,17 +1834,42 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
       constexpr int kRuns = ORCG_FLAT_RUNS;
       static_assert(kRuns == 1 || kRuns == 2, "flat runs in flight");
       uint32_t flat_runs = 0;
+      // kOptFlat16: W=64 runs go through flat_expand16, whose chunk loads
+      // read up to 15 bytes past the run: no such run ends closer than 16
+      // bytes to the descriptor's end (a run the margin excludes is left to
+      // the window loop, like any other end of the chain)
+      constexpr bool kF16 = (kOpt & kOptFlat16) != 0;
+      constexpr int kRuns16 = (kOpt & kOptF16Runs2) ? 2 : (kOpt & kOptF16Runs3) ? 3 : (kOpt & kOptF16Runs5) ? 5
+                                                                                                        : ORCG_FLAT16_RUNS;
+      static_assert(kRuns16 == 2 || kRuns16 == 3 || kRuns16 == 5, "flat 16-byte runs in flight");
+      constexpr bool kSt16 = (kOpt & kOptF16St16) != 0 || (ORCG_FLAT16_STORE16 != 0 && (kOpt & kOptF16St8) == 0);
+      uint32_t lim64 = (uint32_t)(flat_end - bias);
+      if constexpr (kF16) {
+        const uint64_t rel_end = seg_end - bias;
+        lim64 = nrec < 16u ? 0u : (uint32_t)(rel_end < nrec - 16u ? rel_end : nrec - 16u);
+      }
       while (vi >= value_begin && vi < vstop && pos < flat_end) {
         const uint64_t kv = (vstop - vi) / 512u;  // whole runs before the next segment's / the last value
         uint32_t nb = 0;
-        const uint32_t m = flat_probe(rs, (uint32_t)(pos - bias), (uint32_t)(flat_end - bias),
+        const uint32_t m = flat_probe(rs, (uint32_t)(pos - bias), (uint32_t)(flat_end - bias), lim64,
                                       kv < 64u ? (uint32_t)kv : 64u, lane, &nb);
         if (m == 0) break;
         const uint32_t B = 2u + 512u * nb;
         const uint32_t d0 = (uint32_t)(pos - bias) + 2u;
         T* const out = dst + (vi - value_begin);
         // wave w takes runs w, w + 4, ...
-        for (uint32_t r = wv; r < m; r += kWaves * kRuns) {
+        bool wide16 = false;
+        if constexpr (kF16) {
+          if (nb == 8u) {
+            wide16 = true;
+            for (uint32_t r = wv; r < m; r += kWaves * kRuns16) {
+              const uint32_t left = (m - r + kWaves - 1) / kWaves;  // this wave's runs from r on
+              flat_expand16<kOpt, kRuns16, kSt16>(rs, d0 + r * B, kWaves * B, left < (uint32_t)kRuns16 ? left : kRuns16,
+                                                  is_signed, (int64_t*)out + 512u * r, kWaves * 512u, lane);
+            }
+          }
+        }
+        for (uint32_t r = wv; !wide16 && r < m; r += kWaves * kRuns) {
           if constexpr (kRuns == 2) {
             if (r + kWaves < m) {
               flat_expand<kOpt, 2>(rs, d0 + r * B, kWaves * B, nb, is_signed, out + 512u * r, kWaves * 512u, lane);
@@ -2180,12 +2315,15 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
 }  // namespace
 
 // Variants (ctx->rlev2_variant, include/orcg.h): 0 = the density-adaptive
-// default; 2-9 pin one instance (the parity tests run each: 6 = the union
+// default; 2-10 pin one instance (the parity tests run each: 6 = the union
 // instance in two passes, the default's below 1.25 B/value; 8 = the same in
 // one pass; 9 = instance 2 without the flat DIRECT path, its in-binary A/B
-// control); 1 = the wave-walk kernel (rlev2_kernels.hip). (The round 1-5
-// tuning instances of the A/B sweeps were removed in round 6.)
-bool rlev2_variant_valid(int v) { return v >= 0 && v <= 9; }
+// control; 10 = instance 2 with the flat path's 8-byte form for every width,
+// the A/B control and parity cover of flat_expand at W=64); 1 = the
+// wave-walk kernel (rlev2_kernels.hip). (The round 1-5 tuning instances of
+// the A/B sweeps were removed in round 6.) An ORCG_FLAT16_STEPS build (A/B
+// only) adds 11-14, the steps of kOptFlat16.
+bool rlev2_variant_valid(int v) { return v >= 0 && v <= kMaxRlev2Variant; }
 
 static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
   // {stamp, byte offset, value index} per launch-wide segment, stamps zeroed
@@ -2422,8 +2560,9 @@ static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t sr
 
   const unsigned grid_s = (unsigned)nsegs;
   switch (variant) {
-    case 2: ORCG_KX(kWide | kOptD3 | kOptFlat, 33, false, 1, 0, 0, grid_s); break;  // 33 KB register-filled serial, no
-                                                                                    // queue, flat DIRECT prologue
+    case 2:  // 33 KB register-filled serial, no queue, flat DIRECT prologue (W=64 runs in 16-byte chunks)
+      ORCG_KX(kWide | kOptD3 | kOptFlat | kOptFlat16, 33, false, 1, 0, 0, grid_s);
+      break;
     case 3: ORCG_DEFERRING(kSer | kOptD3, 21, 6, kSer | kOptD3); break;   // 21 KB serial + dense drain
     case 4: ORCG_KX(kSer | kOptD3, 8, false, 6, 2, 0, grid_s); break;   // dense v3, 8.5 KB
     case 5: ORCG_KX(kSer | kOptD3, 12, false, 5, 2, 0, grid_s); break;  // dense v3, 12.5 KB
@@ -2439,6 +2578,15 @@ static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t sr
     case 7: ORCG_DEFERRING(kWide | kOptD3, 33, 1, kSer | kOptD3); break;  // 33 KB serial + dense drain (round-3 default, A/B)
     case 8: ORCG_KX(kSer | kOptD3 | kOptUnion, 8, false, 6, 2, 0, grid_s); break;  // union in one pass (round-5 default)
     case 9: ORCG_KX(kWide | kOptD3, 33, false, 1, 0, 0, grid_s); break;  // 2 without the flat prologue (A/B control)
+    case 10: ORCG_KX(kWide | kOptD3 | kOptFlat, 33, false, 1, 0, 0, grid_s); break;  // 2 without kOptFlat16 (A/B control)
+#ifdef ORCG_FLAT16_STEPS
+    // kOptFlat16 one step at a time: 16-byte loads with 8-byte stores (two
+    // runs in flight), with 16-byte stores, then 8-byte stores with 3 and 5 runs
+    case 11: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs2 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
+    case 12: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs2 | kOptF16St16, 33, false, 1, 0, 0, grid_s); break;
+    case 13: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs3 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
+    case 14: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs5 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
+#endif
     default: return set_error(ctx, ORCG_INVALID_ARGUMENT, "unknown RLEv2 kernel variant");
   }
 #undef ORCG_DEFERRING
@@ -2508,7 +2656,7 @@ int stage_table(Ctx* ctx, const void* src, size_t bytes, const void** out) {
   return hip_check(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream), "H2D jobs");
 }
 
-bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 9); }
+bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 10); }
 
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out) {
   const int pinned = ctx->rlev2_variant;
@@ -2522,19 +2670,19 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     return ORCG_OK;
   }
   // one launch per instance: group the streams by the instance they get
-  std::vector<RleJob> group[10];
+  std::vector<RleJob> group[11];
   for (uint32_t j = 0; j < njobs; ++j) {
     const RleJob& J = jobs[j];
     if (J.nsegs == 0 || J.nvalues == 0) continue;
     group[pinned ? pinned : default_variant(J.src_len, J.nvalues)].push_back(J);
   }
   if (debug_on("jobs"))
-    for (int v = 2; v <= 9; ++v)
+    for (int v = 2; v <= 10; ++v)
       for (const RleJob& J : group[v])
         fprintf(stderr, "rle job: instance %d bytes %llu values %llu segments %llu (%.3f B/value)\n", v,
                 (unsigned long long)J.src_len, (unsigned long long)J.nvalues, (unsigned long long)J.nsegs,
                 (double)J.src_len / (double)J.nvalues);
-  for (int v = 2; v <= 9; ++v) {
+  for (int v = 2; v <= 10; ++v) {
     std::vector<RleJob>& g = group[v];
     if (g.empty()) continue;
     // workgroups start in index order: the streams with the most stream
