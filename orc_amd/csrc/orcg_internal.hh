@@ -201,12 +201,8 @@ void warm_rlev2_expand(hipStream_t s);
 // 1 wave-walk, and pins of single tiled instances (launch_rlev2_tiled): 2-8
 // the default's instances and their one-pass / drain forms, 9 = 2 without the
 // flat DIRECT prologue, 10 = 2 with the prologue's 8-byte form at every width
-// (no 16-byte chunks for W=64). An ORCG_FLAT16_STEPS build (A/B) adds 11-14.
-#ifdef ORCG_FLAT16_STEPS
-constexpr int kMaxRlev2Variant = 14;
-#else
+// (no 16-byte chunks for W=64).
 constexpr int kMaxRlev2Variant = 10;
-#endif
 bool rlev2_variant_valid(int v);
 // d_count (may be null): the value count on the device, nvalues then
 // bounds the output only.
@@ -248,6 +244,9 @@ struct MultiLaunch {
   uint32_t spg = 0, slice = 0;
 };
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out);
+// One planned RLEv2 launch (kind 0) over its staged job table, on ctx's stream:
+// run_multi's entry into the tiled instances (rlev2_tiled.hip).
+int launch_rlev2_tiled_jobs(Ctx* ctx, const MultiLaunch& m);
 // A varint DATA stream's tile counts and their scan (the first value of each
 // kVarintTile-byte tile) ahead of its decode: the decimal columns' first two
 // launches, run before the batch's join (they need only the stream bytes).

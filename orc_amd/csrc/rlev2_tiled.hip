@@ -16,15 +16,13 @@
 // runs are at most kMaxRun bytes, so they end inside it. The next window
 // starts at the first unprocessed run.
 //
-// Two structures (template kPipe):
-//  * kPipe = false: all 4 waves fill one window, wave 0 walks, 4 waves expand.
-//  * kPipe = true : wave 0 is the producer (fill window k+1 by LDS-DMA, wait,
-//    walk it) while waves 1-3 expand window k; double-buffered windows and
-//    run tables, one raw s_barrier per window. The producer never stores and
-//    the consumers never wait on vmcnt, so output stores stay in flight across
-//    windows.
+// All 4 waves fill the window; wave 0 walks it and publishes work items as
+// they close, and every wave (wave 0 once its walk is done) claims and
+// expands them, so the walk overlaps the expansion. Dense-capable instances
+// discover the runs of short-run windows in parallel instead (dense mode,
+// below), and the wide-value instance takes a segment's leading chain of
+// equal full DIRECT runs straight from memory (the flat path, flat_*).
 #include <algorithm>
-#include <cstring>
 #include <type_traits>
 #include <vector>
 
@@ -91,17 +89,11 @@ constexpr uint32_t kVparFrag = ORCG_VPAR_FRAG;  // short-run groups per 64 runs 
 #endif
 // its 16-byte form for W=64 runs (kOptFlat16): runs in flight per wave, 2, 3
 // or 5 (a wave's share of a 10,000-row segment: measured 1.1 % faster than 2 on
-// C2, 3 within noise of 2), and whether a value pair is one 16-byte store when
-// the output is 16-byte aligned (measured 0.8 % slower than two 8-byte stores:
-// off). DESIGN.md §4.
+// C2, 3 within noise of 2). DESIGN.md §4.
 #ifndef ORCG_FLAT16_RUNS
 #define ORCG_FLAT16_RUNS 5
 #endif
-#ifndef ORCG_FLAT16_STORE16
-#define ORCG_FLAT16_STORE16 0
-#endif
 constexpr uint32_t kNone = 0xffffffffu;
-constexpr uint32_t kDpErr = 0x80000000u;     // DP entry: a corrupt run starts here
 constexpr uint16_t kSink = 0xffffu;          // chain successor: none
 constexpr uint32_t kWalkDone = 0x80000000u;  // published-runs flag: the walk has finished
 // density hysteresis (stream bytes per run of the last pass)
@@ -118,35 +110,23 @@ constexpr uint32_t kToDense = 24, kToSerial = 64;
 #endif
 constexpr uint32_t kTabToDense = ORCG_TAB_TO_DENSE, kTabToSerial = ORCG_TAB_TO_SERIAL;
 
-// kOpt bits
-constexpr int kOptNTStore = 1;  // non-temporal output stores (streamed, never re-read)
-constexpr int kOptNTLoad = 2;   // non-temporal LDS-DMA loads of the stream
-constexpr int kOptReuse = 4;    // carry the window tail over in LDS; never load past the segment
-constexpr int kOptFast = 8;     // predicate-free paths for full (512-value) runs inside the output range
-constexpr int kOptRegFill = 16; // fill windows through registers (16 B buffer loads, then LDS writes), not LDS-DMA
-constexpr int kOptT4 = 32;
-constexpr int kOptD3 = 64;      // dense discovery: predicated chain marks, wave-reduced control atomics, inline probe
-constexpr int kOptDirect = 128; // dense expansion: lanes store their short runs' values straight to the output (no stage)
-constexpr int kOptPair = 256;   // full DIRECT runs: two values per lane, one 16-byte store (16-byte aligned int64 output)
-constexpr int kOptUnion = 1024; // dense v2 instance whose serial (long-run) windows also cover the dense stage and
-                                // marks: one instance routes each window by its runs (dense or serial), no queue
-constexpr int kOptScan = 4096;      // dense discovery: block entries by a wave scan of entry-state functions (DPP,
-                                    // no LDS gathers), the pointer-doubling chain only when a run jumps too far
-constexpr int kOptPrefetch = 2048;  // register-filled serial windows: every wave loads its share of the next window
-                                    // into registers as soon as the walk is done, while it expands this one
-constexpr int kOptGrpT = 8192;      // serial groups of short runs (one lane per run, scattered 8-byte stores):
-                                    // temporal stores, so L2 merges the partial lines before they reach HBM
-constexpr int kOptTable = 16384;    // two-pass (RunTab): dense passes write their runs to the run table for
-                                    // rlev2_expand_kernel instead of expanding them
-constexpr int kOptFlat = 32768;     // a segment's leading chain of equal full DIRECT runs of >= 40 bits (int64
-                                    // output): one header probe, then expanded straight from memory (flat_*),
-                                    // no LDS window, no walk, no barrier
-constexpr int kOptFlat16 = 65536;   // kOptFlat's W=64 runs: aligned 16-byte chunk loads shifted in registers, two
-                                    // values per lane, ORCG_FLAT16_RUNS runs in flight (flat_expand16)
-// A/B steps of kOptFlat16 (variants 11-14 of an ORCG_FLAT16_STEPS build only):
-// runs in flight other than ORCG_FLAT16_RUNS, 8-byte stores
-constexpr int kOptF16Runs2 = 1 << 17, kOptF16Runs3 = 1 << 18, kOptF16Runs5 = 1 << 19, kOptF16St8 = 1 << 20,
-              kOptF16St16 = 1 << 21;
+// kOpt bits: what an instance adds to the common code. (Output stores are
+// non-temporal, the window's tail is carried over in LDS, full runs inside the
+// output range take predicate-free paths and dense discovery probes inline in
+// every instance; the alternatives measured and rejected are in DESIGN.md §4.)
+// The values keep the positions they had among the retired bits (gaps): the
+// kernels' symbols carry them, and the profiling build's data section is laid
+// out by those symbols.
+constexpr int kOptRegFill = 16;    // fill windows through registers (16 B buffer loads, then LDS writes), not LDS-DMA
+constexpr int kOptUnion = 1024;    // dense instance whose serial (long-run) windows also cover the dense stage and
+                                   // marks: one instance routes each window by its runs (dense or serial), no queue
+constexpr int kOptTable = 16384;   // two-pass (RunTab): dense passes write their runs to the run table for
+                                   // rlev2_expand_kernel instead of expanding them
+constexpr int kOptFlat = 32768;    // a segment's leading chain of equal full DIRECT runs of >= 40 bits (int64
+                                   // output): one header probe, then expanded straight from memory (flat_*),
+                                   // no LDS window, no walk, no barrier
+constexpr int kOptFlat16 = 65536;  // kOptFlat's W=64 runs: aligned 16-byte chunk loads shifted in registers, two
+                                   // values per lane, ORCG_FLAT16_RUNS runs in flight (flat_expand16)
 
 // Debug build only (ORCG_AB_FLAGS=-DORCG_DEBUG_COVER): every expansion path
 // counts the values of the runs it expands; each pass checks the count
@@ -163,21 +143,10 @@ __device__ __forceinline__ uint32_t* s_cover_ptr() {
   } while (0)
 #endif
 
-template <int kOpt, typename T>
+// output stores are non-temporal: streamed, never re-read
+template <typename T>
 __device__ __forceinline__ void store1(T* p, uint64_t v) {
-  if constexpr ((kOpt & kOptNTStore) != 0) __builtin_nontemporal_store((T)(int64_t)v, p);
-  else *p = (T)(int64_t)v;
-}
-
-typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-// two consecutive int64 values, one 16-byte store (p 16-byte aligned)
-template <int kOpt>
-__device__ __forceinline__ void store2(int64_t* p, uint64_t a, uint64_t b) {
-  u64x2 v;
-  v.x = a;
-  v.y = b;
-  if constexpr ((kOpt & kOptNTStore) != 0) __builtin_nontemporal_store(v, (u64x2*)p);
-  else *(u64x2*)p = v;
+  __builtin_nontemporal_store((T)(int64_t)v, p);
 }
 
 __device__ __forceinline__ uint32_t lds_byte(const uint32_t* w, uint32_t o) {
@@ -226,7 +195,7 @@ struct LaneWin {
 };
 
 // Expand one run (already validated by the walk) with one wave.
-template <int kOpt, typename T>
+template <typename T>
 __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords, uint32_t hoff, uint64_t v0,
                                            int is_signed, uint64_t value_begin, uint64_t value_end, T* dst,
                                            int lane) {
@@ -284,52 +253,14 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
 
   if (r.kind == 0) {
     const uint64_t o = v0 + (uint64_t)lane;
-    if ((uint32_t)lane < L && o >= value_begin && o < value_end) store1<kOpt>(dst + (o - value_begin), r.a);
+    if ((uint32_t)lane < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), r.a);
     return;
   }
   if (r.kind == 1) {
     const uint32_t W = r.W;
-    if ((kOpt & kOptFast) && L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
+    if (L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
       // Full run entirely inside the output range: no per-value predicates.
       T* out = dst + (v0 - value_begin);
-      if constexpr ((kOpt & kOptPair) != 0 && sizeof(T) == 8) {
-        if ((((uintptr_t)out) & 15u) == 0) {
-          // lane pairs of values: a wave stores 1 KB per instruction
-          if (W == 64) {
-            const uint32_t r4 = d & 3u;
-#pragma unroll
-            for (int it = 0; it < kMaxRunUnroll / 2; ++it) {
-              const uint32_t j = 2u * (uint32_t)(it * kWave + lane);
-              const uint32_t i = (d + 8u * j) >> 2;
-              const uint32_t w0 = win[i], w1 = win[i + 1], w2 = win[i + 2], w3 = win[i + 3], w4 = win[i + 4];
-              uint64_t a = ((uint64_t)__builtin_bswap32(__builtin_amdgcn_alignbyte(w1, w0, r4)) << 32) |
-                           __builtin_bswap32(__builtin_amdgcn_alignbyte(w2, w1, r4));
-              uint64_t b = ((uint64_t)__builtin_bswap32(__builtin_amdgcn_alignbyte(w3, w2, r4)) << 32) |
-                           __builtin_bswap32(__builtin_amdgcn_alignbyte(w4, w3, r4));
-              if (is_signed) {
-                a = unzigzag(a);
-                b = unzigzag(b);
-              }
-              store2<kOpt>((int64_t*)out + j, a, b);
-            }
-          } else {
-#pragma unroll
-            for (int it = 0; it < kMaxRunUnroll / 2; ++it) {
-              const uint32_t j = 2u * (uint32_t)(it * kWave + lane);
-              const uint32_t bit = j * W, bit2 = bit + W;
-              const uint32_t br = d + (bit >> 3), br2 = d + (bit2 >> 3);
-              uint64_t a = field(lds12(win, br), br, bit & 7u, W);
-              uint64_t b = field(lds12(win, br2), br2, bit2 & 7u, W);
-              if (is_signed) {
-                a = unzigzag(a);
-                b = unzigzag(b);
-              }
-              store2<kOpt>((int64_t*)out + j, a, b);
-            }
-          }
-          return;
-        }
-      }
       if (W == 64) {
         // 8 bytes per value at d + 8j: one uniform byte alignment per run
         const uint32_t r4 = d & 3u;
@@ -341,7 +272,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
           const uint32_t hi = __builtin_amdgcn_alignbyte(w.z, w.y, r4);
           uint64_t v = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
           if (is_signed) v = unzigzag(v);
-          store1<kOpt>(out + j, v);
+          store1(out + j, v);
         }
       } else {
 #pragma unroll
@@ -351,7 +282,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
           const uint32_t br = d + (bit >> 3);
           uint64_t v = field(lds12(win, br), br, bit & 7u, W);
           if (is_signed) v = unzigzag(v);
-          store1<kOpt>(out + j, v);
+          store1(out + j, v);
         }
       }
       return;
@@ -365,7 +296,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
         uint64_t v = field(lds12(win, br), br, bit & 7u, W);
         if (is_signed) v = unzigzag(v);
         const uint64_t o = v0 + j;
-        if (j < L && o >= value_begin && o < value_end) store1<kOpt>(dst + (o - value_begin), v);
+        if (j < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), v);
       }
     }
     return;
@@ -407,7 +338,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
         first = false;
       }
     }
-    if ((kOpt & kOptFast) && L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
+    if (L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
       // full run inside the output range: all 8 chunks' literals in
       // registers, the (few) patches OR-ed into the lane that owns their
       // position, then predicate-free stores
@@ -428,7 +359,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
           if (c == (uint32_t)(it * kWave + lane)) lit[it] |= add;
       }
 #pragma unroll
-      for (int it = 0; it < kMaxRunUnroll; ++it) store1<kOpt>(out + it * kWave + lane, r.a + lit[it]);
+      for (int it = 0; it < kMaxRunUnroll; ++it) store1(out + it * kWave + lane, r.a + lit[it]);
       return;
     }
     uint64_t todo = applied;
@@ -448,7 +379,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
         todo &= todo - 1;
       }
       const uint64_t o = v0 + j;
-      if (j < L && o >= value_begin && o < value_end) store1<kOpt>(dst + (o - value_begin), r.a + lit);
+      if (j < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), r.a + lit);
     }
     return;
   }
@@ -459,7 +390,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
       const uint32_t j = it * kWave + lane;
       const uint64_t o = v0 + j;
       if ((uint32_t)it < niter && j < L && o >= value_begin && o < value_end)
-        store1<kOpt>(dst + (o - value_begin), r.a + (uint64_t)j * r.b);
+        store1(dst + (o - value_begin), r.a + (uint64_t)j * r.b);
     }
     return;
   }
@@ -467,7 +398,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
   const uint64_t v1 = r.a + r.b;
   const bool neg = (int64_t)r.b < 0;
   uint64_t carry = 0;  // wave-uniform running |delta| total
-  if (W <= 26 && (kOpt & kOptFast) && L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
+  if (W <= 26 && L == 512 && v0 >= value_begin && v0 + 512 <= value_end) {
     // full run inside the output range: all 8 chunks' deltas loaded up
     // front, no per-value predicates, one 32-bit wave scan per chunk
     T* out = dst + (v0 - value_begin);
@@ -488,7 +419,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
       const uint64_t sum = carry + s32;
       carry += (uint32_t)__builtin_amdgcn_readlane((int)s32, 63);
       const uint64_t v = j == 0 ? r.a : (j == 1 ? v1 : (neg ? v1 - sum : v1 + sum));
-      store1<kOpt>(out + j, v);
+      store1(out + j, v);
     }
     return;
   }
@@ -509,7 +440,7 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
       carry += (uint32_t)__builtin_amdgcn_readlane((int)s32, 63);
       const uint64_t v = j == 0 ? r.a : (j == 1 ? v1 : (neg ? v1 - sum : v1 + sum));
       const uint64_t o = v0 + j;
-      if (j < L && o >= value_begin && o < value_end) store1<kOpt>(dst + (o - value_begin), v);
+      if (j < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), v);
     }
     return;
   }
@@ -527,19 +458,8 @@ __device__ __forceinline__ void expand_run(const uint32_t* win, uint32_t nwords,
     carry = last_lane(sum);
     const uint64_t v = j == 0 ? r.a : (j == 1 ? v1 : (neg ? v1 - sum : v1 + sum));
     const uint64_t o = v0 + j;
-    if (j < L && o >= value_begin && o < value_end) store1<kOpt>(dst + (o - value_begin), v);
+    if (j < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), v);
   }
-}
-
-// Fill `bytes` (multiple of 1 KB) of LDS at `win` from descriptor offset
-// `wrel` with `nw` waves (wave index `w`).
-template <int kOpt>
-__device__ __forceinline__ void fill(uint32_t* win, __amdgpu_buffer_rsrc_t rs, uint32_t wrel,
-                                     uint32_t bytes, int w, int nw, int lane) {
-  for (uint32_t off = w * 1024u; off < bytes; off += nw * 1024u)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)((char*)win + off),
-                                             16, wrel + off + lane * 16, 0, 0,
-                                             (kOpt & kOptNTLoad) ? 2 : 0);
 }
 
 // The flat DIRECT path (kOptFlat). A writer emits a wide random column as
@@ -592,7 +512,7 @@ __device__ __forceinline__ uint32_t flat_probe(__amdgpu_buffer_rsrc_t rs, uint32
 // out + q * ostep. Each lane loads the three dwords at the aligned-down
 // address of its value (expand_run's extract, from memory instead of LDS);
 // all of the loads are issued before the first store.
-template <int kOpt, int kRuns, typename T>
+template <int kRuns, typename T>
 __device__ __forceinline__ void flat_expand(__amdgpu_buffer_rsrc_t rs, uint32_t d, uint32_t dstep, uint32_t nb,
                                             int is_signed, T* out, uint32_t ostep, int lane) {
   u32x3 w[kRuns][kMaxRunUnroll];
@@ -615,7 +535,7 @@ __device__ __forceinline__ void flat_expand(__amdgpu_buffer_rsrc_t rs, uint32_t 
       const uint32_t rel = d + (uint32_t)q * dstep + j * nb;
       uint64_t v = field(w[q][it], rel, 0, 8u * nb);
       if (is_signed) v = unzigzag(v);
-      store1<kOpt>(out + (uint32_t)q * ostep + j, v);
+      store1(out + (uint32_t)q * ostep + j, v);
     }
   }
 }
@@ -634,8 +554,7 @@ __device__ __forceinline__ void flat_expand(__amdgpu_buffer_rsrc_t rs, uint32_t 
 // range check (the run's start is the scalar offset): the caller takes a run this way only if it ends 16
 // bytes or more before the descriptor's end. cnt <= kRuns runs (q-th at
 // d + q * dstep, values at out + q * ostep), all loads before the first
-// store; a pair is two 8-byte stores, or (kSt16) one 16-byte store when `out`
-// is 16-byte aligned (ostep is even).
+// store; a pair is two 8-byte stores.
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // lane i takes lane i + 1's x (wave_shl:1), lane 63 takes `last`
@@ -643,9 +562,9 @@ __device__ __forceinline__ uint32_t next_lane(uint32_t x, uint32_t last) {
   return (uint32_t)__builtin_amdgcn_update_dpp((int)last, (int)x, 0x130, 0xf, 0xf, false);
 }
 
-template <int kOpt, int K>
+template <int K>
 __device__ __forceinline__ void flat16_run(const u32x4 (&c)[4], uint32_t e, int e0, uint32_t r, int is_signed,
-                                           bool st16, int64_t* out, int lane) {
+                                           int64_t* out, int lane) {
 #pragma unroll
   for (int it = 0; it < 4; ++it) {
     uint32_t D[8];
@@ -663,16 +582,12 @@ __device__ __forceinline__ void flat16_run(const u32x4 (&c)[4], uint32_t e, int 
     }
     // the lane's 16 bytes + a constant: the loads' vector offset serves the stores too
     int64_t* const o = (int64_t*)((char*)out + 16u * (uint32_t)lane) + 2 * kWave * it;
-    if (st16) {
-      store2<kOpt>(o, v[0], v[1]);
-    } else {
-      store1<kOpt>(o, v[0]);
-      store1<kOpt>(o + 1, v[1]);
-    }
+    store1(o, v[0]);
+    store1(o + 1, v[1]);
   }
 }
 
-template <int kOpt, int kRuns, bool kSt16>
+template <int kRuns>
 __device__ __forceinline__ void flat_expand16(__amdgpu_buffer_rsrc_t rs, uint32_t d, uint32_t dstep, uint32_t cnt,
                                               int is_signed, int64_t* out, uint32_t ostep, int lane) {
   cnt = uni(cnt);
@@ -696,17 +611,16 @@ __device__ __forceinline__ void flat_expand16(__amdgpu_buffer_rsrc_t rs, uint32_
   const uint32_t eq = (uint32_t)lane >> 2 < cnt ? (uint32_t)lane >> 2 : cnt - 1u;
   const uint32_t e =
       __builtin_amdgcn_raw_buffer_load_b32(rs, ((d + eq * dstep) & ~15u) + 4096u + 4u * ((uint32_t)lane & 3u), 0, 2);
-  const bool st16 = kSt16 && uni((uint32_t)(uintptr_t)out & 15u) == 0;
 #pragma unroll
   for (int q = 0; q < kRuns; ++q) {
     if ((uint32_t)q < cnt) {
       const uint32_t s = (d + (uint32_t)q * dstep) & 15u;
       int64_t* const o = out + (uint32_t)q * ostep;
       switch (s >> 2) {
-        case 0: flat16_run<kOpt, 0>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
-        case 1: flat16_run<kOpt, 1>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
-        case 2: flat16_run<kOpt, 2>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
-        default: flat16_run<kOpt, 3>(c[q], e, 4 * q, s & 3u, is_signed, st16, o, lane); break;
+        case 0: flat16_run<0>(c[q], e, 4 * q, s & 3u, is_signed, o, lane); break;
+        case 1: flat16_run<1>(c[q], e, 4 * q, s & 3u, is_signed, o, lane); break;
+        case 2: flat16_run<2>(c[q], e, 4 * q, s & 3u, is_signed, o, lane); break;
+        default: flat16_run<3>(c[q], e, 4 * q, s & 3u, is_signed, o, lane); break;
       }
     }
   }
@@ -730,7 +644,6 @@ constexpr uint32_t kItemMax = ORCG_ITEM_MAX;  // short runs per group (<= 64)
 // bytes, DELTA from a terminator mask of the 24 bytes after its header
 // (two varints of <= 11 bytes: every writer's); PATCHED_BASE and longer
 // varints through parse_run.
-template <bool kT4>
 __device__ __forceinline__ void walk_extent(const LaneWin& hw, uint32_t lp, uint32_t avail, int is_signed,
                                             uint32_t* bytes, uint32_t* L, uint32_t* err, uint32_t* rkind) {
   const uint32_t fb = hw.byte(lp), kind = fb >> 6;
@@ -759,19 +672,9 @@ __device__ __forceinline__ void walk_extent(const LaneWin& hw, uint32_t lp, uint
     // (the slice's per-dword terminator nibbles, gathered and realigned)
     const uint32_t o = lp + 2u - hw.base, i0 = o >> 2, sh = o & 3u;
     uint32_t t = 0;
-    if constexpr (kT4) {
 #pragma unroll
-      for (uint32_t k = 0; k < 7; ++k) t |= rdlane(hw.t4, i0 + k) << (4 * k);
-      t = (t >> sh) & 0xffffffu;
-    } else {
-      uint32_t prev = rdlane(hw.word, i0);
-#pragma unroll
-      for (uint32_t k = 0; k < 6; ++k) {
-        const uint32_t nx = rdlane(hw.word, i0 + k + 1);
-        t |= term4(__builtin_amdgcn_alignbyte(nx, prev, sh)) << (4 * k);
-        prev = nx;
-      }
-    }
+    for (uint32_t k = 0; k < 7; ++k) t |= rdlane(hw.t4, i0 + k) << (4 * k);
+    t = (t >> sh) & 0xffffffu;
     const uint32_t n1 = t ? (uint32_t)__builtin_ctz(t) + 1u : 32u;
     const uint32_t t2 = n1 < 24 ? t >> n1 : 0u;
     const uint32_t n2 = t2 ? (uint32_t)__builtin_ctz(t2) + 1u : 32u;
@@ -803,14 +706,14 @@ __device__ __forceinline__ void walk_extent(const LaneWin& hw, uint32_t lp, uint
 // segment, or the table is full. With `pub` the
 // walk also cuts the runs into work items (`items`, ends by run index) and
 // publishes the item count as items close, so expanding waves start early.
-template <uint32_t kWin, uint32_t kCap, bool kT4 = false, typename OffT = uint32_t>
+// (`cap` is kCap at every call; it stays a run-time argument because the
+// compiler lays the walk's loop out differently for a literal bound.)
+template <uint32_t kWin, uint32_t kCap, typename OffT>
 __device__ __forceinline__ WalkResult walk(const uint32_t* win, OffT* run_off, uint32_t* run_val,
                                            uint64_t wpos, uint64_t pos, uint64_t vi, uint64_t seg_end,
                                            uint64_t src_len, uint64_t value_end, int is_signed,
-                                           unsigned long long* err, int lane, uint32_t lim = kWin,
-                                           uint32_t cap = kCap, uint32_t* pub = nullptr,
-                                           uint16_t* items = nullptr, uint32_t probe_n = 0,
-                                           bool probe_values = false) {
+                                           unsigned long long* err, int lane, uint32_t lim, uint32_t cap,
+                                           uint32_t* pub, uint16_t* items, uint32_t probe_n, bool probe_values) {
   static_assert(kCap < kItemLong, "run indices must leave the item flag free");
   constexpr uint32_t kChunk = kWin - kMaxRun;
   // everything wave-uniform and 32-bit, relative to the window / the first
@@ -863,7 +766,7 @@ __device__ __forceinline__ WalkResult walk(const uint32_t* win, OffT* run_off, u
       rL = kind ? L2 : (fb & 7u) + 3u;
     } else {
       uint32_t kd;
-      walk_extent<kT4>(hw, lp, a_src - lp, is_signed, &rbytes, &rL, &e, &kd);
+      walk_extent(hw, lp, a_src - lp, is_signed, &rbytes, &rL, &e, &kd);
       rbytes = uni(rbytes);  // keep the merged values scalar
       rL = uni(rL);
       e = uni(e);
@@ -949,11 +852,10 @@ __device__ __forceinline__ uint64_t short_value(const uint32_t* win, const Run& 
 
 // Expand runs [r0, r1) (r1 - r0 <= 64, each SHORT_REPEAT / DIRECT / DELTA of
 // <= kShortL values) one lane per run, storing straight to the output.
-template <int kOpt, typename T, typename OffT>
+template <typename T, typename OffT>
 __device__ __forceinline__ void group_expand(const uint32_t* win, const OffT* s_off, const uint32_t* s_val,
                                              uint32_t r0, uint32_t r1, uint64_t vi, int is_signed,
                                              uint64_t value_begin, uint64_t value_end, T* dst, int lane) {
-  constexpr int kGrpOpt = (kOpt & kOptGrpT) != 0 ? (kOpt & ~kOptNTStore) : kOpt;
   const uint32_t r = r0 + (uint32_t)lane;
   const bool act = r < r1;
   const uint32_t hoff = act ? s_off[r] : s_off[r0];
@@ -974,7 +876,7 @@ __device__ __forceinline__ void group_expand(const uint32_t* win, const OffT* s_
     ORCG_COVER_ADD(L);
     for (uint32_t j = 0; __ballot(j < L) != 0; ++j) {
       const uint64_t o = o0 + j;
-      if (j < L && o >= value_begin && o < value_end) store1<kGrpOpt>(dst + (o - value_begin), a);
+      if (j < L && o >= value_begin && o < value_end) store1(dst + (o - value_begin), a);
     }
     return;
   }
@@ -986,7 +888,7 @@ __device__ __forceinline__ void group_expand(const uint32_t* win, const OffT* s_
     const uint64_t o = o0 + j;
     if (j < L) {
       const uint64_t x = short_value(win, run, hoff, j, is_signed, acc);
-      if (o >= value_begin && o < value_end) store1<kGrpOpt>(dst + (o - value_begin), x);
+      if (o >= value_begin && o < value_end) store1(dst + (o - value_begin), x);
     }
   }
 }
@@ -1012,19 +914,17 @@ __device__ __forceinline__ uint32_t checked_run(const uint32_t* win, uint32_t lq
   return e;
 }
 
-// ---- dense mode v2 -----------------------------------------------------
-// The same contract as dense_discover, restructured for the CDNA issue model
-// (the v1 code spent ~3.7 SALU instructions per decoded value on exec-mask
-// bookkeeping of divergent branches):
+// ---- dense discovery ---------------------------------------------------
+// Shaped for the CDNA issue model (divergent branches cost SALU exec-mask
+// bookkeeping per decoded value):
 //  * the speculative header parse at every position is branch-free (all
 //    kinds computed, selected by kind) and the in-block DP lives in
 //    registers, indexed at compile time (select chains), not through LDS;
 //  * PATCHED_BASE headers and DELTA varints over 10 bytes are "unknown" to
-//    the DP: a block whose path meets one re-walks exactly (checked_run), as
-//    v1 does for corrupt runs; such a block also ends the pass;
-//  * the chain keeps each thread's 8 successors in registers and one u16 LDS
-//    slot per position (single-buffered: a barrier on each side of the
-//    write); marks propagate only from threads holding a marked position;
+//    the DP: a block whose path meets one re-walks exactly (checked_run);
+//    such a block also ends the pass;
+//  * the chain goes by hops over two u16 LDS tables (block exits, 64-byte
+//    super-block exits), three barriers;
 //  * a block's runs come from a forward pass over the DP registers (no
 //    header re-parse), appended to the run table with predicated writes.
 constexpr uint32_t kDpUnknown = 0x80000000u;
@@ -1035,7 +935,7 @@ __device__ __forceinline__ uint32_t fbs_width_nb(uint32_t code) {
   return code < 24 ? code + 1 : hi;
 }
 
-template <int kOpt, typename OffT>
+template <typename OffT>
 __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT* s_off, uint32_t* s_val,
                                                        uint16_t* s_nxt, uint32_t* s_mark, uint32_t* s_ctl,
                                                        uint64_t wpos, uint32_t sb, uint32_t lim, uint64_t vi,
@@ -1123,93 +1023,15 @@ __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT
     }
   }
   PROF_MARK(3);
-  // (2) every block's entry on the chain from slab position 0
+  // (2) every block's entry on the chain from slab position 0, by hops:
+  // O(slab) work in three barriers. ta = each position's block exit; tb = its
+  // 64-byte super-block exit (<= 7 hops over ta, every thread for its 8
+  // positions); one lane hops the <= 32 super-blocks from position 0 and
+  // records each one's first chain position; every thread hops from its
+  // super-block's entry to its own block (<= 7 hops).
   bool has = false;
   uint32_t eb = 0;
-  bool chained = false;
-  if constexpr ((kOpt & kOptScan) != 0) {
-    // f_t: entry state -> entry state of block t + 1, over 16 states (0-7:
-    // offset in block t; 8-15: offset in block t + 1, block t skipped), one
-    // byte each (0x80 = dead: unknown run, or past the pass's limit); a wave
-    // inclusive scan of the compositions (DPP, no LDS) gives each block's
-    // entry; a run from an entry that jumps past the next two blocks cannot
-    // be expressed, and sends the slab to the pointer-doubling chain below
-    // when (and only when) the chain itself takes it
-    uint32_t fd[4];
-    uint32_t ovf = 0;
-#pragma unroll
-    for (int x = 0; x < 16; ++x) {
-      uint32_t y;
-      if (x < (int)kBlk) {
-        const uint32_t en = ent[x];
-        const uint32_t q = en & 0x7fffu;
-        const bool dead = (en & kDpUnknown) || q >= lim;
-        const uint32_t rel = q - (lo + kBlk);
-        const bool far = !dead && rel >= 16u;
-        ovf |= far ? (1u << x) : 0u;
-        y = (dead || far) ? 0x80u : rel;
-      } else {
-        y = (uint32_t)x - kBlk;
-      }
-      if ((x & 3) == 0) fd[x >> 2] = y;
-      else fd[x >> 2] |= y << (8 * (x & 3));
-    }
-    auto fget = [](const uint32_t* d, uint32_t y) -> uint32_t {
-      const uint32_t w = y < 8u ? (y < 4u ? d[0] : d[1]) : (y < 12u ? d[2] : d[3]);
-      return (w >> ((y & 3u) * 8u)) & 0xffu;
-    };
-    // own <- own o fetched (fetched applied first); lanes without a source
-    // keep the identity (bound_ctrl off: the old operand)
-    auto step = [&](auto ctrl_tag, auto mask_tag) {
-      constexpr int kCtrl = decltype(ctrl_tag)::value, kMask = decltype(mask_tag)::value;
-      const uint32_t idn[4] = {0x03020100u, 0x07060504u, 0x0B0A0908u, 0x0F0E0D0Cu};
-      uint32_t f[4], r[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        f[k] = (uint32_t)__builtin_amdgcn_update_dpp((int)idn[k], (int)fd[k], kCtrl, kMask, 0xf, false);
-#pragma unroll
-      for (int x = 0; x < 16; ++x) {
-        const uint32_t y = (f[x >> 2] >> (8 * (x & 3))) & 0xffu;
-        const uint32_t z = y < 16u ? fget(fd, y) : 0x80u;
-        if ((x & 3) == 0) r[x >> 2] = z;
-        else r[x >> 2] |= z << (8 * (x & 3));
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) fd[k] = r[k];
-    };
-    step(std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});  // row_shr:1
-    step(std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});  // row_shr:2
-    step(std::integral_constant<int, 0x114>{}, std::integral_constant<int, 0xf>{});  // row_shr:4
-    step(std::integral_constant<int, 0x118>{}, std::integral_constant<int, 0xf>{});  // row_shr:8
-    step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});  // row_bcast:15
-    step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});  // row_bcast:31
-    // the wave totals through LDS (the marks' words are free here)
-    if (lane == kWave - 1) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) s_mark[4 * wave + k] = fd[k];
-    }
-    if (tid == 0) s_mark[16] = 0;
-    __syncthreads();
-    uint32_t xw = 0;  // the wave's entry state: the slab starts at position 0
-    for (int w = 0; w < wave; ++w) {
-      const uint32_t t[4] = {s_mark[4 * w], s_mark[4 * w + 1], s_mark[4 * w + 2], s_mark[4 * w + 3]};
-      xw = xw < 16u ? fget(t, xw) : 0x80u;
-    }
-    const uint32_t nxt = xw < 16u ? fget(fd, xw) : 0x80u;  // block t + 1's entry state
-    const uint32_t cur = (uint32_t)__builtin_amdgcn_update_dpp((int)xw, (int)nxt, 0x138, 0xf, 0xf, false);  // wave_shr:1
-    has = cur < kBlk;
-    eb = has ? cur : 0u;
-    const bool bad = has && ((ovf >> eb) & 1u);
-    if (__ballot(bad) != 0 && lane == 0) s_mark[16] = 1u;
-    __syncthreads();
-    chained = s_mark[16] != 0;
-    if (chained) __syncthreads();  // every wave has read the flag before the chain rewrites the marks
-  } else {
-    chained = true;
-  }
-  if (chained) {
-    // (2) the chain from slab position 0 by pointer doubling over two
-    // successor tables (read one, write the other: one barrier per level)
+  {
     uint32_t na[kBlk];
   #pragma unroll
     for (int e = 0; e < (int)kBlk; ++e) {
@@ -1228,14 +1050,6 @@ __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT
     uint16_t* ta = s_nxt;
     uint16_t* tb = s_nxt + kSlab;
     put8(ta);
-#ifndef ORCG_DOUBLING_CHAIN
-    // (2) the chain by hops, O(slab) work in three barriers: ta = each
-    // position's block exit; tb = its 64-byte super-block exit (<= 7 hops
-    // over ta, every thread for its 8 positions); one lane hops the <= 32
-    // super-blocks from position 0 and records each one's first chain
-    // position; every thread hops from its super-block's entry to its own
-    // block (<= 7 hops). The pointer doubling below (ORCG_DOUBLING_CHAIN)
-    // took 8 levels of marks and gathers over the whole slab.
     constexpr uint32_t kSup = 8u * kBlk;
     __syncthreads();
     {
@@ -1277,43 +1091,6 @@ __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT
       eb = has ? p - lo : 0u;
     }
     static_assert(kSlab / kSup <= kSlab / 32, "super-block entries fit the marks");
-#else
-    if (tid < (int)(kSlab / 32)) s_mark[tid] = tid == 0;  // position 0 starts the chain
-    __syncthreads();
-  #pragma unroll 1
-    for (int lev = 0; lev < 8; ++lev) {
-      const uint32_t m8 = (s_mark[lo >> 5] >> (lo & 31u)) & 0xffu;
-      if (m8) {
-        // marked positions mark their successor (marks only grow, and every
-        // marked position is a chain element, so racing with this level's
-        // readers is harmless)
-  #pragma unroll
-        for (int e = 0; e < (int)kBlk; ++e) {
-          const bool go = ((m8 >> e) & 1u) && na[e] != kSink;
-          if constexpr ((kOpt & kOptD3) != 0) {
-            if (go) atomicOr(&s_mark[na[e] >> 5], 1u << (na[e] & 31u));
-          } else {
-            const uint32_t n = go ? na[e] : 0u;
-            atomicOr(&s_mark[n >> 5], go ? 1u << (n & 31u) : 0u);
-          }
-        }
-      }
-  #pragma unroll
-      for (int e = 0; e < (int)kBlk; ++e) {
-        const bool valid = na[e] != kSink;
-        const uint32_t v = ta[valid ? na[e] : lo + (uint32_t)e];
-        na[e] = valid ? v : (uint32_t)kSink;
-      }
-      put8(tb);
-      uint16_t* t = ta;
-      ta = tb;
-      tb = t;
-      __syncthreads();
-    }
-    const uint32_t mb = (s_mark[lo >> 5] >> (lo & 31u)) & 0xffu;
-    has = mb != 0;
-    eb = has ? (uint32_t)__builtin_ctz(mb) : 0u;
-#endif
   }
   PROF_MARK(4);
   // (3) the block's entry, its runs (a forward pass over the DP registers),
@@ -1386,14 +1163,11 @@ __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT
     v_end = v;
     s_ctl[14] = cnt;
   }
-  if constexpr ((kOpt & kOptD3) != 0) {
+  {
     // one atomic per wave: its first stopped lane, its last lane with an entry
     const uint64_t bs = __ballot(has && stopped), bh = __ballot(has);
     if (bs && lane == __builtin_ctzll(bs)) atomicMin(&s_ctl[12], (uint32_t)tid);
     if (bh && lane == 63 - __builtin_clzll(bh)) atomicMax(&s_ctl[13], (uint32_t)tid);
-  } else if (has) {
-    if (stopped) atomicMin(&s_ctl[12], (uint32_t)tid);
-    atomicMax(&s_ctl[13], (uint32_t)tid);
   }
   // the successor tables are dead: the run table may overwrite them
   __syncthreads();
@@ -1421,7 +1195,7 @@ __device__ __forceinline__ DenseResult dense2_discover(const uint32_t* win, OffT
 // consecutive short runs (<= kStage values) are decoded one lane per run into
 // the wave's LDS stage and flushed with coalesced stores; any other run
 // (long, PATCHED_BASE) goes through expand_run.
-template <int kOpt, typename T, typename OffT>
+template <typename T, typename OffT>
 __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nwords, const OffT* s_off,
                                              const uint32_t* s_val, uint64_t* stage, uint32_t r0, uint32_t r1,
                                              uint64_t vi, int is_signed, uint64_t value_begin, uint64_t value_end,
@@ -1470,12 +1244,11 @@ __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nword
     const bool shortr = sh0 && !vpr;
     const uint32_t Ls = shortr ? run.L : 0u;
     const uint32_t incl = wave_scan_u32(Ls);
-    constexpr bool kStraight = (kOpt & kOptDirect) != 0;
     // every run parsed here is expanded before the next 64 are parsed
     // (a mix of short and long runs, e.g. low-cardinality dictionary
     // indices, used to parse its 64 headers again after every long run):
-    // first the runs of consecutive short runs, through the stage (or
-    // straight), then each long / PATCHED_BASE run by the whole wave, once
+    // first the runs of consecutive short runs, through the stage,
+    // then each long / PATCHED_BASE run by the whole wave, once
     // the parsed runs are dead (fewer live registers around expand_run)
     const uint32_t nact = r1 - c < (uint32_t)kWave ? r1 - c : (uint32_t)kWave;
     const uint64_t longm = __ballot(act && !vpr && !shortr);
@@ -1522,7 +1295,7 @@ __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nword
             if (kind == 3) x = ak + (uint64_t)j * bk;
           }
           const uint64_t g = vi + vk + j;
-          if (o < Tv && g >= value_begin && g < value_end) store1<kOpt>(dst + (g - value_begin), x);
+          if (o < Tv && g >= value_begin && g < value_end) store1(dst + (g - value_begin), x);
         }
         ORCG_COVER_ADD(vpr ? run.L : 0u);
       }
@@ -1531,31 +1304,13 @@ __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nword
       const uint32_t a = (uint32_t)__builtin_ctzll(rem);
       // short runs [a, b): consecutive in the output; a stage-full at most
       const uint32_t base = a ? rdlane(incl, a - 1) : 0u;
-      const uint64_t stop_m = __ballot((uint32_t)lane >= a && (!shortr || (!kStraight && incl - base > kStage)));
+      const uint64_t stop_m = __ballot((uint32_t)lane >= a && (!shortr || incl - base > kStage));
       uint32_t b = stop_m ? (uint32_t)__builtin_ctzll(stop_m) : (uint32_t)kWave;
       if (b > nact) b = nact;
       rem &= b >= (uint32_t)kWave ? 0ull : ~((1ull << b) - 1ull);
       const bool mine = (uint32_t)lane >= a && (uint32_t)lane < b;
       const uint32_t myl = mine ? Ls : 0u;
       ORCG_COVER_ADD(myl);
-      if constexpr (kStraight) {
-        // each lane stores its run's values at their output positions
-        const uint64_t g0 = vi + val;
-        if (__ballot(mine && run.kind != 0) == 0) {
-          for (uint32_t j = 0; __ballot(j < myl) != 0; ++j) {
-            const uint64_t g = g0 + j;
-            if (j < myl && g >= value_begin && g < value_end) store1<kOpt>(dst + (g - value_begin), run.a);
-          }
-        } else {
-          uint64_t acc = 0;
-          for (uint32_t j = 0; __ballot(j < myl) != 0; ++j) {
-            const uint64_t g = g0 + j;
-            const uint64_t x = j < myl ? short_value(win, run, hoff, j, is_signed, acc) : 0ull;
-            if (j < myl && g >= value_begin && g < value_end) store1<kOpt>(dst + (g - value_begin), x);
-          }
-        }
-        continue;
-      }
       const uint32_t st0 = incl - Ls - base;
       if (__ballot(mine && run.kind != 0) == 0) {
         for (uint32_t j = 0; __ballot(j < myl) != 0; ++j)
@@ -1571,7 +1326,7 @@ __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nword
       const uint64_t g0 = vi + rdlane(val, a);
       for (uint32_t o = (uint32_t)lane; o < tot; o += kWave) {
         const uint64_t g = g0 + o;
-        if (g >= value_begin && g < value_end) store1<kOpt>(dst + (g - value_begin), stage[o]);
+        if (g >= value_begin && g < value_end) store1(dst + (g - value_begin), stage[o]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
@@ -1582,21 +1337,15 @@ __device__ __forceinline__ void dense_expand(const uint32_t* win, uint32_t nword
       if (lane == 0) ORCG_COVER_ADD(parse_run([&](uint32_t i) { return lds_byte(win, uni(s_off[c + a]) + i); }, ~0ull,
                                               kHdrLim, is_signed).L);
 #endif
-      expand_run<kOpt>(win, nwords, uni(s_off[c + a]), vi + uni(s_val[c + a]), is_signed, value_begin, value_end, dst,
-                       lane);
+      expand_run(win, nwords, uni(s_off[c + a]), vi + uni(s_val[c + a]), is_signed, value_begin, value_end, dst, lane);
     }
     c += nact;
   }
 }
 
-__device__ __forceinline__ void lds_barrier() {
-  // LDS ordering only: never drains the output stores (vmcnt).
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-// Dense v2 LDS: the run table (u16 window offsets, u32 value offsets) shares
-// its bytes with the chain's single successor table (dead once the runs are
-// emitted); per-wave value stages; chain marks.
+// Dense LDS: the run table (u16 window offsets, u32 value offsets) shares
+// its bytes with the chain's two exit tables (dead once the runs are
+// emitted); per-wave value stages; the super-blocks' chain entries (mark).
 struct Dense2Lds {
   union {
     struct {
@@ -1633,8 +1382,7 @@ struct Dense2TabLds {
 // static share, so a short-run segment never runs the one-wave header walk,
 // whatever the stream's overall density. Entries of older launches carry
 // older stamps: nothing is ever reset.
-template <typename T, bool kPositions, int kOpt, int kWinKB, bool kPipe, int kMinWaves, int kDense = 0, int kDefer = 0,
-          bool kMulti = false>
+template <typename T, bool kPositions, int kOpt, int kWinKB, int kMinWaves, int kDense, int kDefer, bool kMulti>
 __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
     const uint8_t* __restrict__ p_src, uint64_t p_src_len, int p_is_signed,
     const uint64_t* __restrict__ p_segtab, uint64_t p_nsegs, uint64_t rows_per_group,
@@ -1655,48 +1403,41 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
   constexpr uint32_t kChunkS = kWinS - kMaxRun;
   static_assert(!kUnion || (kWin + 32) % 8 == 0, "stage alignment");
   static_assert(!kDense || kChunk % kSlab == 0, "dense window chunk must be whole slabs");
-  constexpr int kBufs = kPipe ? 2 : 1;
-  static_assert(!(kDense && kPipe), "dense mode is a non-pipelined instance");
-  // run table capacity; in dense v1 instances the slab DP table aliases it
-  constexpr uint32_t kCap = kDense ? kDenseRuns : 512u;
-  static_assert(!kDense || 2 * kCap >= kSlab, "DP table must fit the run table");
+  static_assert(kDense == 0 || kDense == 2, "kDense: 0 serial only, 2 dense-capable");
+  constexpr uint32_t kCap = kDense ? kDenseRuns : 512u;  // run table capacity
   static_assert(!kDense || kChunk >= kSlab, "window too small for a slab");
   using OffT = typename std::conditional<kDense == 2, uint16_t, uint32_t>::type;
-  __shared__ __attribute__((aligned(16))) uint32_t s_win[kBufs][kWinS / 4 + 8];  // + 32 B: the 12-byte extract may read past a run
-  __shared__ uint32_t s_ctl[kBufs][16];
+  __shared__ __attribute__((aligned(16))) uint32_t s_win[kWinS / 4 + 8];  // + 32 B: the 12-byte extract may read past a run
+  __shared__ uint32_t s_ctl[16];
   __shared__ uint32_t s_sync[2][2];  // serial passes: {published runs, claimed runs}, by pass parity
-  OffT* s_off[kBufs];
-  uint32_t* s_val[kBufs];
-  uint16_t* s_nxt2 = nullptr;   // v2: successor table, marks, stages
+  OffT* s_off = nullptr;
+  uint32_t* s_val = nullptr;
+  uint16_t* s_nxt2 = nullptr;   // dense: successor tables, marks, stages
   uint32_t* s_mark2 = nullptr;
   uint64_t* s_stage2 = nullptr;
-  uint16_t* s_items = nullptr;  // serial passes (non-pipelined): work item ends
+  uint16_t* s_items = nullptr;  // serial passes: work item ends
   if constexpr (kUnion) {
     __shared__ __attribute__((aligned(16))) Dense2TabLds s_d2;
     s_items = s_d2.tab.items;
-    s_off[0] = s_d2.tab.off;
-    s_val[0] = s_d2.tab.val;
+    s_off = s_d2.tab.off;
+    s_val = s_d2.tab.val;
     s_nxt2 = s_d2.nxt;
-    s_stage2 = (uint64_t*)((char*)s_win[0] + kWin + 32);
-    s_mark2 = (uint32_t*)((char*)s_win[0] + kWin + 32 + kWaves * kStage * 8);
+    s_stage2 = (uint64_t*)((char*)s_win + kWin + 32);
+    s_mark2 = (uint32_t*)((char*)s_win + kWin + 32 + kWaves * kStage * 8);
   } else if constexpr (kDense == 2) {
     __shared__ __attribute__((aligned(16))) Dense2Lds s_d2;
     s_items = s_d2.tab.items;
-    s_off[0] = s_d2.tab.off;
-    s_val[0] = s_d2.tab.val;
+    s_off = s_d2.tab.off;
+    s_val = s_d2.tab.val;
     s_nxt2 = s_d2.nxt;
     s_mark2 = s_d2.mark;
     s_stage2 = &s_d2.stage[0][0];
   } else {
-    __shared__ uint32_t s_tab[kBufs][2 * kCap];
-    for (int b = 0; b < kBufs; ++b) {
-      s_off[b] = s_tab[b];
-      s_val[b] = s_tab[b] + kCap;
-    }
-    if constexpr (!kPipe) {
-      __shared__ uint16_t s_itm[kCap];
-      s_items = s_itm;
-    }
+    __shared__ uint32_t s_tab[2 * kCap];
+    __shared__ uint16_t s_itm[kCap];
+    s_off = s_tab;
+    s_val = s_tab + kCap;
+    s_items = s_itm;
   }
 
   const int tid = (int)threadIdx.x;
@@ -1814,7 +1555,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
   uint32_t sync_par = 0;
   if (tid < 4) s_sync[tid >> 1][tid & 1] = 0;  // ordered before use by the first window's barrier
   PROF_DECL;
-  if constexpr ((kOpt & kOptFlat) != 0 && sizeof(T) == 8 && !kPipe && kDense == 0 && kDefer == 0) {
+  if constexpr ((kOpt & kOptFlat) != 0 && sizeof(T) == 8 && kDense == 0 && kDefer == 0) {
     // The flat prologue (flat_probe / flat_expand above): the segment's
     // leading chain of equal full DIRECT runs of >= 40 bits, taken only while
     // the runs lie wholly inside the requested values and end at or before
@@ -1839,10 +1580,8 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
       // bytes to the descriptor's end (a run the margin excludes is left to
       // the window loop, like any other end of the chain)
       constexpr bool kF16 = (kOpt & kOptFlat16) != 0;
-      constexpr int kRuns16 = (kOpt & kOptF16Runs2) ? 2 : (kOpt & kOptF16Runs3) ? 3 : (kOpt & kOptF16Runs5) ? 5
-                                                                                                        : ORCG_FLAT16_RUNS;
+      constexpr int kRuns16 = ORCG_FLAT16_RUNS;
       static_assert(kRuns16 == 2 || kRuns16 == 3 || kRuns16 == 5, "flat 16-byte runs in flight");
-      constexpr bool kSt16 = (kOpt & kOptF16St16) != 0 || (ORCG_FLAT16_STORE16 != 0 && (kOpt & kOptF16St8) == 0);
       uint32_t lim64 = (uint32_t)(flat_end - bias);
       if constexpr (kF16) {
         const uint64_t rel_end = seg_end - bias;
@@ -1864,19 +1603,19 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
             wide16 = true;
             for (uint32_t r = wv; r < m; r += kWaves * kRuns16) {
               const uint32_t left = (m - r + kWaves - 1) / kWaves;  // this wave's runs from r on
-              flat_expand16<kOpt, kRuns16, kSt16>(rs, d0 + r * B, kWaves * B, left < (uint32_t)kRuns16 ? left : kRuns16,
-                                                  is_signed, (int64_t*)out + 512u * r, kWaves * 512u, lane);
+              flat_expand16<kRuns16>(rs, d0 + r * B, kWaves * B, left < (uint32_t)kRuns16 ? left : kRuns16, is_signed,
+                                     (int64_t*)out + 512u * r, kWaves * 512u, lane);
             }
           }
         }
         for (uint32_t r = wv; !wide16 && r < m; r += kWaves * kRuns) {
           if constexpr (kRuns == 2) {
             if (r + kWaves < m) {
-              flat_expand<kOpt, 2>(rs, d0 + r * B, kWaves * B, nb, is_signed, out + 512u * r, kWaves * 512u, lane);
+              flat_expand<2>(rs, d0 + r * B, kWaves * B, nb, is_signed, out + 512u * r, kWaves * 512u, lane);
               continue;
             }
           }
-          flat_expand<kOpt, 1>(rs, d0 + r * B, 0, nb, is_signed, out + 512u * r, 0, lane);
+          flat_expand<1>(rs, d0 + r * B, 0, nb, is_signed, out + 512u * r, 0, lane);
         }
         pos += (uint64_t)m * B;
         vi += 512ull * m;
@@ -1891,395 +1630,289 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
 #endif
     }
   }
-  if constexpr (!kPipe) {
-    uint64_t pwpos = ~0ull;  // previous window (stream offset) and its valid bytes
-    uint32_t pneed = 0;
-    // kOptPrefetch: the next window's bytes, loaded into registers during
-    // the previous window's expansion (pf_wrel: its descriptor offset)
-    constexpr bool kPf = (kOpt & kOptPrefetch) != 0 && (kOpt & kOptRegFill) != 0 && (kOpt & kOptReuse) != 0 &&
-                         kDense == 0;
-    typedef uint32_t pf_u4 __attribute__((ext_vector_type(4)));
-    constexpr int kPfPer = kPf ? (int)((kWinS + kThreads * 16 - 1) / (kThreads * 16)) : 1;
-    pf_u4 pf[kPfPer];
-    uint32_t pf_wrel = ~0u, pf_need = 0;
-    // wave-uniform mode of the next pass (dense instances only): the
-    // segment's first pass is a short serial probe (32 runs in v1, 4 in v2)
-    // whose bytes per run pick the mode
-    bool dense = queued;
-    bool probe = !queued;
-    if constexpr (kDense == 2 && (kOpt & kOptD3) != 0) {
-      // queued segments (short runs by values) are sized by the inline
-      // probe too: dense discovery for short runs in bytes, the serial walk
-      // with staged group expansion for wide ones
-      dense = false;
-      probe = true;
+  uint64_t pwpos = ~0ull;  // previous window (stream offset) and its valid bytes
+  uint32_t pneed = 0;
+  // wave-uniform mode of the next pass (dense instances only): the bytes per
+  // run of the segment's first runs pick it (the inline probe below; queued
+  // segments, short runs by values, are sized by it too: dense discovery for
+  // short runs in bytes, the serial walk with staged group expansion for wide
+  // ones)
+  bool dense = false;
+  bool probe = true;
+  while (pos < seg_end && vi < value_end) {
+    const uint32_t wrel = (uint32_t)(pos - bias) & ~15u;
+    const uint64_t wpos = bias + wrel;
+    // union instances: a window whose runs are known to be long (the probe
+    // is done and the mode is serial) is a serial window of kWinS bytes:
+    // serial passes only, short-run groups expanded without the stage
+    const bool big = kUnion && !dense && !probe;
+    uint32_t need = big ? kWinS : kWin, keep = 0;
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    // never load past the segment: its runs end at seg_end
+    const uint64_t end_rel = (seg_end - bias + 15) & ~15ull;
+    if (end_rel - wrel < need) need = (uint32_t)(end_rel - wrel);
+    // the previous window's tail [wpos, pwpos + pneed) is already in LDS:
+    // move it to the front instead of re-reading it (source and
+    // destination must not overlap: the shift is at least the length;
+    // otherwise reload)
+    if (pwpos != ~0ull && pwpos + pneed > wpos && wpos - pwpos >= pwpos + pneed - wpos) {
+      keep = (uint32_t)(pwpos + pneed - wpos);
+      if (keep > need) keep = need;
+      const uint32_t so = (uint32_t)(wpos - pwpos);
+      for (uint32_t o = tid * 16u; o < keep; o += kThreads * 16u)
+        *(u4*)((char*)s_win + o) = *(const u4*)((const char*)s_win + so + o);
+      __syncthreads();  // reads of the tail finish before the DMA below lands
     }
-    while (pos < seg_end && vi < value_end) {
-      const uint32_t wrel = (uint32_t)(pos - bias) & ~15u;
-      const uint64_t wpos = bias + wrel;
-      // union instances: a window whose runs are known to be long (the probe
-      // is done and the mode is serial) is a serial window of kWinS bytes:
-      // serial passes only, short-run groups expanded without the stage
-      const bool big = kUnion && !dense && !probe;
-      uint32_t need = big ? kWinS : kWin, keep = 0;
-      if constexpr ((kOpt & kOptReuse) != 0) {
-        // never load past the segment: its runs end at seg_end
-        const uint64_t end_rel = (seg_end - bias + 15) & ~15ull;
-        if (end_rel - wrel < need) need = (uint32_t)(end_rel - wrel);
-        // the previous window's tail [wpos, pwpos + pneed) is already in LDS:
-        // move it to the front instead of re-reading it (source and
-        // destination must not overlap: the shift is at least the length;
-        // otherwise reload)
-        const bool prefetched = kPf && pf_wrel == wrel && pf_need == need;
-        if (!prefetched && pwpos != ~0ull && pwpos + pneed > wpos && wpos - pwpos >= pwpos + pneed - wpos) {
-          keep = (uint32_t)(pwpos + pneed - wpos);
-          if (keep > need) keep = need;
-          const uint32_t so = (uint32_t)(wpos - pwpos);
-          typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-          for (uint32_t o = tid * 16u; o < keep; o += kThreads * 16u)
-            *(u4*)((char*)s_win[0] + o) = *(const u4*)((const char*)s_win[0] + so + o);
-          __syncthreads();  // reads of the tail finish before the DMA below lands
-        }
-        if constexpr ((kOpt & kOptRegFill) != 0) {
-          // every lane issues all of its 16-byte loads before the first LDS
-          // write (measured: +4 % over LDS-DMA on a pure window copy)
-          typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-          constexpr int kPer = (kWinS + kThreads * 16 - 1) / (kThreads * 16);
-          if (kPf && prefetched) {
-            // the whole window arrived in registers during the last expansion
+    if constexpr ((kOpt & kOptRegFill) != 0) {
+      // every lane issues all of its 16-byte loads before the first LDS
+      // write (measured: +4 % over LDS-DMA on a pure window copy)
+      constexpr int kPer = (kWinS + kThreads * 16 - 1) / (kThreads * 16);
+      u4 v[kPer];
 #pragma unroll
-            for (int i = 0; i < kPfPer; ++i) {
-              const uint32_t off = (uint32_t)(i * kThreads + tid) * 16u;
-              if (off < need) *(u4*)((char*)s_win[0] + off) = __builtin_bit_cast(u4, pf[i]);
-            }
-          } else {
-            u4 v[kPer];
-#pragma unroll
-            for (int i = 0; i < kPer; ++i) {
-              const uint32_t off = keep + (uint32_t)(i * kThreads + tid) * 16u;
-              if (off < need)
-                v[i] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rs, wrel + off, 0, 2));
-            }
-#pragma unroll
-            for (int i = 0; i < kPer; ++i) {
-              const uint32_t off = keep + (uint32_t)(i * kThreads + tid) * 16u;
-              if (off < need) *(u4*)((char*)s_win[0] + off) = v[i];
-            }
-          }
-          pf_wrel = ~0u;
-        } else {
-          for (uint32_t off = keep + wave * 1024u; off < need; off += kWaves * 1024u)
-            if (off + lane * 16u < need)
-              __builtin_amdgcn_raw_ptr_buffer_load_lds(
-                  rs, (__attribute__((address_space(3))) void*)((char*)s_win[0] + off), 16,
-                  wrel + off + lane * 16u, 0, 0, (kOpt & kOptNTLoad) ? 2 : 0);
-        }
-      } else {
-        fill<kOpt>(s_win[0], rs, wrel, kWin, wave, kWaves, lane);
+      for (int i = 0; i < kPer; ++i) {
+        const uint32_t off = keep + (uint32_t)(i * kThreads + tid) * 16u;
+        if (off < need) v[i] = __builtin_bit_cast(u4, __builtin_amdgcn_raw_buffer_load_b128(rs, wrel + off, 0, 2));
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      PROF_MARK(0);
-      if constexpr (kDense == 2 && (kOpt & kOptD3) != 0) {
-        // inline probe (no serial pass): one lane sizes the segment's first
-        // runs; short ones (< kToDense stream bytes each) start it dense
-        if (probe) {
-          if (tid == 0) {
-            uint32_t p = (uint32_t)(pos - wpos), nb = 0, nr = 0;
-            while (nr < 4 && nb < 4 * kDenseB && p + kHdrLim < need) {
-              const Run r = parse_run([&](uint32_t i) { return lds_byte(s_win[0], p + i); }, ~0ull, kHdrLim, is_signed);
-              if (r.err != kErrNone || r.kind == 2) break;
-              nb += r.bytes;
-              p += r.bytes;
-              ++nr;
-            }
-            s_ctl[0][15] = (nr == 4 && nb < 4 * kDenseB) ? 1u : 0u;
-          }
-          __syncthreads();
-          dense = uni(s_ctl[0][15]) != 0;
-          probe = false;
-        }
-      }
-      // every run that starts in the window's first kChunk bytes ends inside
-      // it: consume them all (several passes) before moving the window
-      do {
-        uint32_t n, stop, dpos, dval, shrt = 0;
-#ifdef ORCG_DEBUG_COVER
-        if (tid == 0) *s_cover_ptr() = 0;
-        __syncthreads();
-#endif
-        bool was_dense = false;
-        bool tabled = false;  // kOptTable: this pass's runs went to the run table
-        if constexpr (kDense) was_dense = dense;
-        if (was_dense) {
-          const uint32_t sb = (uint32_t)(pos - wpos);
-          const uint32_t lim = min(kSlab, kChunk - sb);
-          DenseResult d;
-          if constexpr (kDense == 2) {
-            d = dense2_discover<kOpt>(s_win[0], s_off[0], s_val[0], s_nxt2, s_mark2, s_ctl[0], wpos, sb, lim, vi, seg_end,
-                                src_len, value_end, need, is_signed, err, tid
-#ifdef ORCG_PHASE_PROF
-                                , prof_last_
-#endif
-            );
-          }
-          n = d.n;
-          stop = d.stop;
-          dpos = d.dpos;
-          dval = d.dval;
-          if constexpr (kTable) {
-            // the runs go to the run table (entry: stream byte offset | first
-            // value in the segment << 32); a run holding slice boundary k * S
-            // is where slice k starts (runs are <= 512 < S values: one each)
-            const uint64_t vrel = vi - vi0;
-            if (vrel + dval <= tlim) {
-              tabled = true;
-              const uint32_t vr = (uint32_t)vrel, S = rtab.slice;
-              for (uint32_t r = (uint32_t)tid; r < n; r += kThreads) {
-                const uint32_t v = vr + s_val[0][r];
-                const uint32_t ve = vr + (r + 1 < n ? s_val[0][r + 1] : dval);
-                ttab[tcnt + r] = (wpos + s_off[0][r]) | ((uint64_t)v << 32);
-                const uint32_t kb = (v + S - 1) / S;
-                if (kb >= 1 && kb * S < ve) thdr[kRtHdr + kb] = tcnt + r;
-              }
-              tcnt += n;
-            }
-          }
-          if constexpr (kDense != 0) {
-            if (!tabled) {
-              uint64_t* const stage = s_stage2 + wave * kStage;
-              const uint32_t r0 = (uint32_t)(((uint64_t)n * wave) / kWaves),
-                             r1 = (uint32_t)(((uint64_t)n * (wave + 1)) / kWaves);
-              dense_expand<kOpt>(s_win[0], kWin / 4 + 8, s_off[0], s_val[0], stage, r0, r1, vi, is_signed,
-                                 value_begin, value_end, dst, lane);
-            }
-          }
-        } else {
-          // Wave 0 walks and publishes work items (a group of short runs or
-          // one long run) as they close; every wave (wave 0 once its walk is
-          // done) claims published items from an LDS counter and expands
-          // them, so the walk overlaps the expansion.
-          uint32_t* s_pub = &s_sync[sync_par][0];
-          uint32_t* s_claim = &s_sync[sync_par][1];
-          if (wave == 0) {
-            // the walk is the workgroup's critical path: raise its issue
-            // priority over co-resident waves that are expanding
-            __builtin_amdgcn_s_setprio(3);
-            // a segment's first walk probes its first runs (4 in dense v2
-            // instances, 8 in queueing serial ones) and stops there when
-            // they are short; a long-run segment just walks on (dense v1:
-            // a separate 32-run probe pass)
-            const uint32_t probe_n = (probe && (kDense == 2 || kDefer == 1)) ? (kDense == 2 ? 4u : 8u) : 0u;
-            constexpr bool kProbeValues = kDefer == 1 && (kOpt & kOptD3) != 0;
-            const uint32_t cap = (kDense == 1 && probe) ? 32u : kCap;
-            const WalkResult w =
-                big ? walk<kWinS, kCap, (kOpt & kOptT4) != 0, OffT>(s_win[0], s_off[0], s_val[0], wpos, pos, vi, seg_end,
-                                                                    src_len, value_end, is_signed, err, lane, need, cap,
-                                                                    s_pub, s_items, probe_n, kProbeValues)
-                    : walk<kWin, kCap, (kOpt & kOptT4) != 0, OffT>(s_win[0], s_off[0], s_val[0], wpos, pos, vi, seg_end,
-                                                                   src_len, value_end, is_signed, err, lane, need, cap,
-                                                                   s_pub, s_items, probe_n, kProbeValues);
-            if (lane == 0) {
-              s_ctl[0][0] = w.n;
-              s_ctl[0][1] = w.stop;
-              s_ctl[0][2] = w.dpos;
-              s_ctl[0][3] = w.dval;
-              s_ctl[0][4] = w.shrt;
-              __hip_atomic_store(s_pub, w.items | kWalkDone, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
-            PROF_MARK(1);  // wave 0's walk of this pass
-#ifdef ORCG_PHASE_PROF
-            if (tid == 0) {
-              atomicAdd(&g_phase[8], (unsigned long long)w.n);  // runs walked
-              atomicAdd(&g_phase[9], 1ull);                     // serial passes
-            }
-#endif
-            __builtin_amdgcn_s_setprio(0);
-          }
-          bool pf_issued = !kPf;
-          for (;;) {
-            uint32_t k = 0;
-            if (lane == 0) k = atomicAdd(s_claim, 1u);
-            k = uni(k);
-            uint32_t pub;
-            // waiting waves back off: polling shares the CU's scalar unit with
-            // the walk (a short-run walk publishes an item every ~64 runs)
-            for (uint32_t spin = 0;; ++spin) {
-              pub = uni(__hip_atomic_load(s_pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-              if (k < (pub & ~kWalkDone) || (pub & kWalkDone)) break;
-              if (spin < 2) __builtin_amdgcn_s_sleep(2);
-              else __builtin_amdgcn_s_sleep(24);
-            }
-            if constexpr (kPf) {
-              if (!pf_issued && (pub & kWalkDone)) {
-                // the walk is done: if this pass ends the window, load this
-                // thread's share of the next one while the items expand
-                pf_issued = true;
-                const uint64_t npos = pos + uni(s_ctl[0][2]);
-                const uint64_t nvi = vi + uni(s_ctl[0][3]);
-                const uint32_t chunk = big ? kChunkS : kChunk;
-                if (!uni(s_ctl[0][1]) && npos >= wpos + chunk && npos < seg_end && nvi < value_end) {
-                  const uint32_t nwrel = (uint32_t)(npos - bias) & ~15u;
-                  const uint64_t end_rel = (seg_end - bias + 15) & ~15ull;
-                  const uint32_t nneed = end_rel - nwrel < kWinS ? (uint32_t)(end_rel - nwrel) : kWinS;
 #pragma unroll
-                  for (int i = 0; i < kPfPer; ++i) {
-                    const uint32_t off = (uint32_t)(i * kThreads + tid) * 16u;
-                    if (off < nneed)
-                      pf[i] = __builtin_bit_cast(pf_u4, __builtin_amdgcn_raw_buffer_load_b128(rs, nwrel + off, 0, 2));
-                  }
-                  pf_wrel = nwrel;
-                  pf_need = nneed;
-                }
-              }
-            }
-            if (k >= (pub & ~kWalkDone)) break;  // the walk is done and every item is claimed
-            const uint32_t e = uni(s_items[k]);
-            const uint32_t r0 = k ? (uni(s_items[k - 1]) & ~(uint32_t)kItemLong) : 0u;
-            if (e & kItemLong) {
-#ifdef ORCG_DEBUG_COVER
-              if (lane == 0) {
-                const uint32_t h = uni(s_off[0][r0]);
-                ORCG_COVER_ADD(parse_run([&](uint32_t i) { return lds_byte(s_win[0], h + i); }, ~0ull, kHdrLim,
-                                         is_signed).L);
-              }
-#endif
-              expand_run<kOpt>(s_win[0], kWinS / 4 + 8, uni(s_off[0][r0]), vi + uni(s_val[0][r0]), is_signed,
-                               value_begin, value_end, dst, lane);
-            }
-            else if (kDense == 2 && (kOpt & kOptD3) != 0 && !big)
-              // coalesced stores through the wave's value stage
-              dense_expand<kOpt>(s_win[0], kWin / 4 + 8, s_off[0], s_val[0], s_stage2 + wave * kStage, r0, e, vi,
-                                 is_signed, value_begin, value_end, dst, lane);
-            else
-              group_expand<kOpt>(s_win[0], s_off[0], s_val[0], r0, e, vi, is_signed, value_begin, value_end, dst,
-                                 lane);
+      for (int i = 0; i < kPer; ++i) {
+        const uint32_t off = keep + (uint32_t)(i * kThreads + tid) * 16u;
+        if (off < need) *(u4*)((char*)s_win + off) = v[i];
+      }
+    } else {
+      // LDS-DMA: 1 KB per wave instruction
+      for (uint32_t off = keep + wave * 1024u; off < need; off += kWaves * 1024u)
+        if (off + lane * 16u < need)
+          __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)((char*)s_win + off),
+                                                   16, wrel + off + lane * 16u, 0, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    PROF_MARK(0);
+    if constexpr (kDense == 2) {
+      // inline probe (no serial pass): one lane sizes the segment's first
+      // runs; short ones (< kToDense stream bytes each) start it dense
+      if (probe) {
+        if (tid == 0) {
+          uint32_t p = (uint32_t)(pos - wpos), nb = 0, nr = 0;
+          while (nr < 4 && nb < 4 * kDenseB && p + kHdrLim < need) {
+            const Run r = parse_run([&](uint32_t i) { return lds_byte(s_win, p + i); }, ~0ull, kHdrLim, is_signed);
+            if (r.err != kErrNone || r.kind == 2) break;
+            nb += r.bytes;
+            p += r.bytes;
+            ++nr;
           }
-          // the other parity's counters are idle: clear them for the next serial pass
-          if (tid == 0) {
-            s_sync[sync_par ^ 1][0] = 0;
-            s_sync[sync_par ^ 1][1] = 0;
-          }
-          sync_par ^= 1;
-          __syncthreads();
-          n = uni(s_ctl[0][0]);
-          stop = uni(s_ctl[0][1]);
-          dpos = uni(s_ctl[0][2]);
-          dval = uni(s_ctl[0][3]);
-          shrt = uni(s_ctl[0][4]);
+          s_ctl[15] = (nr == 4 && nb < 4 * kDenseB) ? 1u : 0u;
         }
-        __syncthreads();  // the run table (and the window) are rewritten next
-#ifdef ORCG_DEBUG_COVER
-        if (tid == 0 && !stop && *s_cover_ptr() != dval) report(err, vi, was_dense ? 0x71u : 0x70u);
         __syncthreads();
-#endif
-        PROF_MARK(was_dense ? 6 : 2);
-#ifdef ORCG_PHASE_PROF
-        if (was_dense) ++wg_dense;
-        else ++wg_serial;
-#endif
-        if constexpr (kTable) {
-          // a pass expanded here: slices starting inside it start at the next
-          // table entry; then the segment header (read by the second pass)
-          const uint64_t vrel = vi - vi0, vend = vrel + dval;
-          if (!tabled) {
-            const uint64_t S = rtab.slice, ve = vend < tlim ? vend : tlim;
-            const uint64_t kb0 = vrel == 0 ? 1u : (vrel + S - 1) / S;
-            for (uint64_t kb = kb0 + (uint64_t)tid; kb * S < ve; kb += kThreads) thdr[kRtHdr + kb] = tcnt;
-          }
-          if (tid == 0) {
-            thdr[0] = tcnt;
-            thdr[1] = vend < 0xffffffffull ? (uint32_t)vend : 0xffffffffu;
-          }
-        }
-        if (stop) return;
-        pos += dpos;
-        vi += dval;
-        const bool was_probe = probe;
+        dense = uni(s_ctl[15]) != 0;
         probe = false;
-        if constexpr (kDefer == 1) {
-          // a short-run segment: queue the rest for the dense instance
-          if (shrt && pos < seg_end && vi < value_end) {
-            if (tid == 0) {
-              // the segment's own entry, stamped with this launch pair's
-              // sequence number (no shared counter: one atomic per queued
-              // segment on one word serialised whole launches)
-              defer_q[3 * gg + 1] = pos;
-              defer_q[3 * gg + 2] = vi;
-              __hip_atomic_store(&defer_q[3 * gg], (unsigned long long)defer_par, __ATOMIC_RELAXED,
-                                 __HIP_MEMORY_SCOPE_AGENT);
-              // the launch-wide "something was queued" word (after the
-              // launch's last segment entry): written once per launch pair
-              // in the common case (a load first, so a stream whose every
-              // segment queues does not serialise on one address)
-              unsigned long long* any = &defer_q[3 * p_nsegs];
-              if (__hip_atomic_load(any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned long long)defer_par)
-                __hip_atomic_store(any, (unsigned long long)defer_par, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            return;
-          }
-        }
-        if constexpr (kDense) {
-          // hysteresis on the stream bytes per run of this pass
-          if (n > 0) {
-            const uint32_t bpr = dpos / n;
-            if (shrt || (!dense && (n >= 8 || (was_probe && n >= 4)) && bpr < kDenseB)) dense = true;
-            else if (dense && bpr >= kSerialB) dense = false;
-          }
-        }
-        if (n == 0 && dpos == 0) break;  // nothing consumed (cannot happen for a good window)
-        // a union instance leaves a serial window as soon as its runs turn
-        // short: the next window is a dense one
-        if (big && dense) break;
-      } while (pos < wpos + (big ? kChunkS : kChunk) && pos < seg_end && vi < value_end);
-      pwpos = wpos;
-      pneed = need;
-    }
-  } else {
-    // prologue: the producer fills and walks window 0
-    if (wave == 0) {
-      const uint32_t wrel = (uint32_t)(pos - bias) & ~15u;
-      fill<kOpt>(s_win[0], rs, wrel, kWin, 0, 1, lane);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      const WalkResult w = walk<kWin, kCap>(s_win[0], s_off[0], s_val[0], bias + wrel, pos, vi, seg_end, src_len,
-                                      value_end, is_signed, err, lane);
-      if (lane == 0) {
-        s_ctl[0][0] = w.n;
-        s_ctl[0][1] = w.stop;
-        s_ctl[0][2] = w.dpos;
-        s_ctl[0][3] = w.dval;
       }
     }
-    lds_barrier();
-    for (uint32_t b = 0;; b ^= 1) {
-      const uint32_t n = uni(s_ctl[b][0]), stop = uni(s_ctl[b][1]);
-      const uint64_t next_pos = pos + uni(s_ctl[b][2]), next_vi = vi + uni(s_ctl[b][3]);
-      const bool more = !stop && next_pos < seg_end && next_vi < value_end;
-      if (wave == 0) {
-        if (more) {  // produce window b^1 while the consumers expand window b
-          const uint32_t wrel = (uint32_t)(next_pos - bias) & ~15u;
-          fill<kOpt>(s_win[b ^ 1], rs, wrel, kWin, 0, 1, lane);
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          const WalkResult w = walk<kWin, kCap>(s_win[b ^ 1], s_off[b ^ 1], s_val[b ^ 1], bias + wrel, next_pos,
-                                          next_vi, seg_end, src_len, value_end, is_signed, err, lane);
-          if (lane == 0) {
-            s_ctl[b ^ 1][0] = w.n;
-            s_ctl[b ^ 1][1] = w.stop;
-            s_ctl[b ^ 1][2] = w.dpos;
-            s_ctl[b ^ 1][3] = w.dval;
+    // every run that starts in the window's first kChunk bytes ends inside
+    // it: consume them all (several passes) before moving the window
+    do {
+      uint32_t n, stop, dpos, dval, shrt = 0;
+#ifdef ORCG_DEBUG_COVER
+      if (tid == 0) *s_cover_ptr() = 0;
+      __syncthreads();
+#endif
+      bool was_dense = false;
+      bool tabled = false;  // kOptTable: this pass's runs went to the run table
+      if constexpr (kDense) was_dense = dense;
+      if (was_dense) {
+        const uint32_t sb = (uint32_t)(pos - wpos);
+        const uint32_t lim = min(kSlab, kChunk - sb);
+        DenseResult d;
+        if constexpr (kDense == 2) {
+          d = dense2_discover(s_win, s_off, s_val, s_nxt2, s_mark2, s_ctl, wpos, sb, lim, vi, seg_end, src_len,
+                              value_end, need, is_signed, err, tid
+#ifdef ORCG_PHASE_PROF
+                              , prof_last_
+#endif
+          );
+        }
+        n = d.n;
+        stop = d.stop;
+        dpos = d.dpos;
+        dval = d.dval;
+        if constexpr (kTable) {
+          // the runs go to the run table (entry: stream byte offset | first
+          // value in the segment << 32); a run holding slice boundary k * S
+          // is where slice k starts (runs are <= 512 < S values: one each)
+          const uint64_t vrel = vi - vi0;
+          if (vrel + dval <= tlim) {
+            tabled = true;
+            const uint32_t vr = (uint32_t)vrel, S = rtab.slice;
+            for (uint32_t r = (uint32_t)tid; r < n; r += kThreads) {
+              const uint32_t v = vr + s_val[r];
+              const uint32_t ve = vr + (r + 1 < n ? s_val[r + 1] : dval);
+              ttab[tcnt + r] = (wpos + s_off[r]) | ((uint64_t)v << 32);
+              const uint32_t kb = (v + S - 1) / S;
+              if (kb >= 1 && kb * S < ve) thdr[kRtHdr + kb] = tcnt + r;
+            }
+            tcnt += n;
+          }
+        }
+        if constexpr (kDense != 0) {
+          if (!tabled) {
+            uint64_t* const stage = s_stage2 + wave * kStage;
+            const uint32_t r0 = (uint32_t)(((uint64_t)n * wave) / kWaves),
+                           r1 = (uint32_t)(((uint64_t)n * (wave + 1)) / kWaves);
+            dense_expand(s_win, kWin / 4 + 8, s_off, s_val, stage, r0, r1, vi, is_signed, value_begin, value_end,
+                         dst, lane);
           }
         }
       } else {
-        for (uint32_t k = wave - 1; k < n; k += kWaves - 1)
-          expand_run<kOpt>(s_win[b], kWin / 4 + 8, uni(s_off[b][k]), vi + uni(s_val[b][k]), is_signed, value_begin,
-                           value_end, dst, lane);
+        // Wave 0 walks and publishes work items (a group of short runs or
+        // one long run) as they close; every wave (wave 0 once its walk is
+        // done) claims published items from an LDS counter and expands
+        // them, so the walk overlaps the expansion.
+        uint32_t* s_pub = &s_sync[sync_par][0];
+        uint32_t* s_claim = &s_sync[sync_par][1];
+        if (wave == 0) {
+          // the walk is the workgroup's critical path: raise its issue
+          // priority over co-resident waves that are expanding
+          __builtin_amdgcn_s_setprio(3);
+          // a segment's first walk probes its first runs (4 in dense
+          // instances, 8 in queueing serial ones) and stops there when
+          // they are short; a long-run segment just walks on
+          const uint32_t probe_n = (probe && (kDense == 2 || kDefer == 1)) ? (kDense == 2 ? 4u : 8u) : 0u;
+          constexpr bool kProbeValues = kDefer == 1;
+          const WalkResult w =
+              big ? walk<kWinS, kCap, OffT>(s_win, s_off, s_val, wpos, pos, vi, seg_end, src_len, value_end, is_signed,
+                                            err, lane, need, kCap, s_pub, s_items, probe_n, kProbeValues)
+                  : walk<kWin, kCap, OffT>(s_win, s_off, s_val, wpos, pos, vi, seg_end, src_len, value_end, is_signed,
+                                           err, lane, need, kCap, s_pub, s_items, probe_n, kProbeValues);
+          if (lane == 0) {
+            s_ctl[0] = w.n;
+            s_ctl[1] = w.stop;
+            s_ctl[2] = w.dpos;
+            s_ctl[3] = w.dval;
+            s_ctl[4] = w.shrt;
+            __hip_atomic_store(s_pub, w.items | kWalkDone, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          PROF_MARK(1);  // wave 0's walk of this pass
+#ifdef ORCG_PHASE_PROF
+          if (tid == 0) {
+            atomicAdd(&g_phase[8], (unsigned long long)w.n);  // runs walked
+            atomicAdd(&g_phase[9], 1ull);                     // serial passes
+          }
+#endif
+          __builtin_amdgcn_s_setprio(0);
+        }
+        for (;;) {
+          uint32_t k = 0;
+          if (lane == 0) k = atomicAdd(s_claim, 1u);
+          k = uni(k);
+          uint32_t pub;
+          // waiting waves back off: polling shares the CU's scalar unit with
+          // the walk (a short-run walk publishes an item every ~64 runs)
+          for (uint32_t spin = 0;; ++spin) {
+            pub = uni(__hip_atomic_load(s_pub, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+            if (k < (pub & ~kWalkDone) || (pub & kWalkDone)) break;
+            if (spin < 2) __builtin_amdgcn_s_sleep(2);
+            else __builtin_amdgcn_s_sleep(24);
+          }
+          if (k >= (pub & ~kWalkDone)) break;  // the walk is done and every item is claimed
+          const uint32_t e = uni(s_items[k]);
+          const uint32_t r0 = k ? (uni(s_items[k - 1]) & ~(uint32_t)kItemLong) : 0u;
+          if (e & kItemLong) {
+#ifdef ORCG_DEBUG_COVER
+            if (lane == 0) {
+              const uint32_t h = uni(s_off[r0]);
+              ORCG_COVER_ADD(parse_run([&](uint32_t i) { return lds_byte(s_win, h + i); }, ~0ull, kHdrLim,
+                                       is_signed).L);
+            }
+#endif
+            expand_run(s_win, kWinS / 4 + 8, uni(s_off[r0]), vi + uni(s_val[r0]), is_signed, value_begin, value_end,
+                       dst, lane);
+          } else if (kDense == 2 && !big) {
+            // coalesced stores through the wave's value stage
+            dense_expand(s_win, kWin / 4 + 8, s_off, s_val, s_stage2 + wave * kStage, r0, e, vi, is_signed,
+                         value_begin, value_end, dst, lane);
+          } else {
+            group_expand(s_win, s_off, s_val, r0, e, vi, is_signed, value_begin, value_end, dst, lane);
+          }
+        }
+        // the other parity's counters are idle: clear them for the next serial pass
+        if (tid == 0) {
+          s_sync[sync_par ^ 1][0] = 0;
+          s_sync[sync_par ^ 1][1] = 0;
+        }
+        sync_par ^= 1;
+        __syncthreads();
+        n = uni(s_ctl[0]);
+        stop = uni(s_ctl[1]);
+        dpos = uni(s_ctl[2]);
+        dval = uni(s_ctl[3]);
+        shrt = uni(s_ctl[4]);
       }
-      lds_barrier();
+      __syncthreads();  // the run table (and the window) are rewritten next
+#ifdef ORCG_DEBUG_COVER
+      if (tid == 0 && !stop && *s_cover_ptr() != dval) report(err, vi, was_dense ? 0x71u : 0x70u);
+      __syncthreads();
+#endif
+      PROF_MARK(was_dense ? 6 : 2);
+#ifdef ORCG_PHASE_PROF
+      if (was_dense) ++wg_dense;
+      else ++wg_serial;
+#endif
+      if constexpr (kTable) {
+        // a pass expanded here: slices starting inside it start at the next
+        // table entry; then the segment header (read by the second pass)
+        const uint64_t vrel = vi - vi0, vend = vrel + dval;
+        if (!tabled) {
+          const uint64_t S = rtab.slice, ve = vend < tlim ? vend : tlim;
+          const uint64_t kb0 = vrel == 0 ? 1u : (vrel + S - 1) / S;
+          for (uint64_t kb = kb0 + (uint64_t)tid; kb * S < ve; kb += kThreads) thdr[kRtHdr + kb] = tcnt;
+        }
+        if (tid == 0) {
+          thdr[0] = tcnt;
+          thdr[1] = vend < 0xffffffffull ? (uint32_t)vend : 0xffffffffu;
+        }
+      }
       if (stop) return;
-      pos = next_pos;
-      vi = next_vi;
-      if (!more) break;
-    }
+      pos += dpos;
+      vi += dval;
+      const bool was_probe = probe;
+      probe = false;
+      if constexpr (kDefer == 1) {
+        // a short-run segment: queue the rest for the dense instance
+        if (shrt && pos < seg_end && vi < value_end) {
+          if (tid == 0) {
+            // the segment's own entry, stamped with this launch pair's
+            // sequence number (no shared counter: one atomic per queued
+            // segment on one word serialised whole launches)
+            defer_q[3 * gg + 1] = pos;
+            defer_q[3 * gg + 2] = vi;
+            __hip_atomic_store(&defer_q[3 * gg], (unsigned long long)defer_par, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+            // the launch-wide "something was queued" word (after the
+            // launch's last segment entry): written once per launch pair
+            // in the common case (a load first, so a stream whose every
+            // segment queues does not serialise on one address)
+            unsigned long long* any = &defer_q[3 * p_nsegs];
+            if (__hip_atomic_load(any, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != (unsigned long long)defer_par)
+              __hip_atomic_store(any, (unsigned long long)defer_par, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          return;
+        }
+      }
+      if constexpr (kDense) {
+        // hysteresis on the stream bytes per run of this pass
+        if (n > 0) {
+          const uint32_t bpr = dpos / n;
+          if (shrt || (!dense && (n >= 8 || (was_probe && n >= 4)) && bpr < kDenseB)) dense = true;
+          else if (dense && bpr >= kSerialB) dense = false;
+        }
+      }
+      if (n == 0 && dpos == 0) break;  // nothing consumed (cannot happen for a good window)
+      // a union instance leaves a serial window as soon as its runs turn
+      // short: the next window is a dense one
+      if (big && dense) break;
+    } while (pos < wpos + (big ? kChunkS : kChunk) && pos < seg_end && vi < value_end);
+    pwpos = wpos;
+    pneed = need;
   }
   if (tid == 0 && v_next != ~0ull && vi < value_end && vi != v_next) report(err, vi, kErrBadSegment);
   if (tid == 0 && v_next == ~0ull && vi < value_end) report(err, vi, kErrBadRead);  // stream ended early
@@ -2320,9 +1953,7 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
 // one pass; 9 = instance 2 without the flat DIRECT path, its in-binary A/B
 // control; 10 = instance 2 with the flat path's 8-byte form for every width,
 // the A/B control and parity cover of flat_expand at W=64); 1 = the
-// wave-walk kernel (rlev2_kernels.hip). (The round 1-5 tuning instances of
-// the A/B sweeps were removed in round 6.) An ORCG_FLAT16_STEPS build (A/B
-// only) adds 11-14, the steps of kOptFlat16.
+// wave-walk kernel (rlev2_kernels.hip).
 bool rlev2_variant_valid(int v) { return v >= 0 && v <= kMaxRlev2Variant; }
 
 static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
@@ -2499,100 +2130,72 @@ static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t sr
   uint32_t dpar = 0;
   (void)cu_count(ctx);
 
-#define ORCG_K(T, P, O, WKB, PIPE, ML)                                                               \
-  hipLaunchKernelGGL((rlev2_tiled_kernel<T, P, O, WKB, PIPE, MW, DN, DF, ML>), grid, block, 0, ctx->stream,   \
+#define ORCG_K(T, P, O, WKB, ML)                                                                          \
+  hipLaunchKernelGGL((rlev2_tiled_kernel<T, P, O, WKB, MW, DN, DF, ML>), grid, block, 0, ctx->stream,     \
                      d_src, src_len, sg, d_segtab, nsegs, rows_per_group, value_begin, nvalues, (T*)d_dst, \
                      ctx->d_err, dq, dpar, jobs_d, njobs_d, dcount, rtab)
-// single-stream instances (+ the multi-stream one for the default's
-// instances, ORCG_KX; the tuning variants have none, ORCG_KX1)
-#define ORCG_KX1(O, WKB, PIPE, MWV, DNV, DFV, GRIDV)                                 \
-  do {                                                                              \
-    constexpr int MW = MWV;                                                         \
-    constexpr int DN = (int)(DNV);                                                  \
-    constexpr int DF = DFV;                                                         \
-    const dim3 grid(GRIDV);                                                         \
-    if (dst_bytes == 8) {                                                           \
-      if (positions_mode) ORCG_K(int64_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int64_t, false, O, WKB, PIPE, false);                              \
-    } else if (dst_bytes == 4) {                                                    \
-      if (positions_mode) ORCG_K(int32_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int32_t, false, O, WKB, PIPE, false);                              \
-    } else {                                                                        \
-      if (positions_mode) ORCG_K(int16_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int16_t, false, O, WKB, PIPE, false);                              \
-    }                                                                               \
+// an instance (options, window KB, min waves, kDense, kDefer): its
+// single-stream kernels and its multi-stream one
+#define ORCG_KX(O, WKB, MWV, DNV, DFV, GRIDV)                 \
+  do {                                                        \
+    constexpr int MW = MWV;                                   \
+    constexpr int DN = (int)(DNV);                            \
+    constexpr int DF = DFV;                                   \
+    const dim3 grid(GRIDV);                                   \
+    if (jobs_d) {                                             \
+      ORCG_K(int64_t, false, O, WKB, true);                   \
+    } else if (dst_bytes == 8) {                              \
+      if (positions_mode) ORCG_K(int64_t, true, O, WKB, false); \
+      else ORCG_K(int64_t, false, O, WKB, false);             \
+    } else if (dst_bytes == 4) {                              \
+      if (positions_mode) ORCG_K(int32_t, true, O, WKB, false); \
+      else ORCG_K(int32_t, false, O, WKB, false);             \
+    } else {                                                  \
+      if (positions_mode) ORCG_K(int16_t, true, O, WKB, false); \
+      else ORCG_K(int16_t, false, O, WKB, false);             \
+    }                                                         \
   } while (0)
-#define ORCG_KX(O, WKB, PIPE, MWV, DNV, DFV, GRIDV)                                  \
-  do {                                                                              \
-    constexpr int MW = MWV;                                                         \
-    constexpr int DN = (int)(DNV);                                                  \
-    constexpr int DF = DFV;                                                         \
-    const dim3 grid(GRIDV);                                                         \
-    if (jobs_d) {                                                                   \
-      ORCG_K(int64_t, false, O, WKB, PIPE, true);                                   \
-    } else if (dst_bytes == 8) {                                                    \
-      if (positions_mode) ORCG_K(int64_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int64_t, false, O, WKB, PIPE, false);                              \
-    } else if (dst_bytes == 4) {                                                    \
-      if (positions_mode) ORCG_K(int32_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int32_t, false, O, WKB, PIPE, false);                              \
-    } else {                                                                        \
-      if (positions_mode) ORCG_K(int16_t, true, O, WKB, PIPE, false);                \
-      else ORCG_K(int16_t, false, O, WKB, PIPE, false);                              \
-    }                                                                               \
-  } while (0)
-#define ORCG_KT(O, WKB, PIPE, MWV, DNV) ORCG_KX1(O, WKB, PIPE, MWV, DNV, 0, grid_s)
 
   // the default's instances
-  constexpr int kSer = kOptNTStore | kOptReuse | kOptFast | kOptT4;  // serial-walk paths
-  constexpr int kWide = kSer | kOptRegFill;
+  constexpr int kSer = 0;             // LDS-DMA windows
+  constexpr int kWide = kOptRegFill;  // register-filled windows
   // a serial instance that queues short-run segments, then the dense
   // instance that drains the queue
-#define ORCG_DEFERRING(O, WKB, MWV, DO)                                               \
-  do {                                                                              \
-    int rc_ = defer_queue(ctx, nsegs, &dq);                                          \
-    if (rc_) return rc_;                                                            \
-    dpar = (uint32_t)(ctx->defer_seq++ % 0xffffffffull) + 1u; /* never 0 */         \
-    ORCG_KX(O, WKB, false, MWV, 0, 1, (unsigned)nsegs);                              \
-    debug_defer(ctx, dq, nsegs, dpar);                                                \
-    ORCG_KX(DO, 8, false, 6, 2, 2, (unsigned)nsegs);                                 \
+#define ORCG_DEFERRING(O, WKB, MWV, DO)                                     \
+  do {                                                                      \
+    int rc_ = defer_queue(ctx, nsegs, &dq);                                 \
+    if (rc_) return rc_;                                                    \
+    dpar = (uint32_t)(ctx->defer_seq++ % 0xffffffffull) + 1u; /* never 0 */ \
+    ORCG_KX(O, WKB, MWV, 0, 1, (unsigned)nsegs);                            \
+    debug_defer(ctx, dq, nsegs, dpar);                                      \
+    ORCG_KX(DO, 8, 6, 2, 2, (unsigned)nsegs);                               \
   } while (0)
 
   const unsigned grid_s = (unsigned)nsegs;
   switch (variant) {
     case 2:  // 33 KB register-filled serial, no queue, flat DIRECT prologue (W=64 runs in 16-byte chunks)
-      ORCG_KX(kWide | kOptD3 | kOptFlat | kOptFlat16, 33, false, 1, 0, 0, grid_s);
+      ORCG_KX(kWide | kOptFlat | kOptFlat16, 33, 1, 0, 0, grid_s);
       break;
-    case 3: ORCG_DEFERRING(kSer | kOptD3, 21, 6, kSer | kOptD3); break;   // 21 KB serial + dense drain
-    case 4: ORCG_KX(kSer | kOptD3, 8, false, 6, 2, 0, grid_s); break;   // dense v3, 8.5 KB
-    case 5: ORCG_KX(kSer | kOptD3, 12, false, 5, 2, 0, grid_s); break;  // dense v3, 12.5 KB
+    case 3: ORCG_DEFERRING(kSer, 21, 6, kSer); break;  // 21 KB serial + dense drain
+    case 4: ORCG_KX(kSer, 8, 6, 2, 0, grid_s); break;   // dense-capable, 8.5 KB
+    case 5: ORCG_KX(kSer, 12, 5, 2, 0, grid_s); break;  // dense-capable, 12.5 KB
     case 6: {
       // union, two passes: dense passes table their runs, rlev2_expand_kernel
       // expands them in value slices
-      ORCG_KX(kSer | kOptD3 | kOptUnion | kOptTable, 8, false, 6, 2, 0, grid_s);
+      ORCG_KX(kSer | kOptUnion | kOptTable, 8, 6, 2, 0, grid_s);
       const int rc = hip_check(ctx, hipGetLastError(), "rlev2_tiled_kernel launch");
       if (rc) return rc;
       return launch_rlev2_expand(ctx, d_src, src_len, sg, value_begin, nvalues, d_dst, dst_bytes, dcount, jobs_d,
                                  njobs_d, nsegs, rtab);
     }
-    case 7: ORCG_DEFERRING(kWide | kOptD3, 33, 1, kSer | kOptD3); break;  // 33 KB serial + dense drain (round-3 default, A/B)
-    case 8: ORCG_KX(kSer | kOptD3 | kOptUnion, 8, false, 6, 2, 0, grid_s); break;  // union in one pass (round-5 default)
-    case 9: ORCG_KX(kWide | kOptD3, 33, false, 1, 0, 0, grid_s); break;  // 2 without the flat prologue (A/B control)
-    case 10: ORCG_KX(kWide | kOptD3 | kOptFlat, 33, false, 1, 0, 0, grid_s); break;  // 2 without kOptFlat16 (A/B control)
-#ifdef ORCG_FLAT16_STEPS
-    // kOptFlat16 one step at a time: 16-byte loads with 8-byte stores (two
-    // runs in flight), with 16-byte stores, then 8-byte stores with 3 and 5 runs
-    case 11: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs2 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
-    case 12: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs2 | kOptF16St16, 33, false, 1, 0, 0, grid_s); break;
-    case 13: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs3 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
-    case 14: ORCG_KX1(kWide | kOptD3 | kOptFlat | kOptFlat16 | kOptF16Runs5 | kOptF16St8, 33, false, 1, 0, 0, grid_s); break;
-#endif
+    case 7: ORCG_DEFERRING(kWide, 33, 1, kSer); break;  // 33 KB serial + dense drain (round-3 default, A/B)
+    case 8: ORCG_KX(kSer | kOptUnion, 8, 6, 2, 0, grid_s); break;  // union in one pass (round-5 default)
+    case 9: ORCG_KX(kWide, 33, 1, 0, 0, grid_s); break;  // 2 without the flat prologue (A/B control)
+    case 10: ORCG_KX(kWide | kOptFlat, 33, 1, 0, 0, grid_s); break;  // 2 without kOptFlat16 (A/B control)
     default: return set_error(ctx, ORCG_INVALID_ARGUMENT, "unknown RLEv2 kernel variant");
   }
 #undef ORCG_DEFERRING
-#undef ORCG_KT
 #undef ORCG_KX
-#undef ORCG_KX1
 #undef ORCG_K
   return hip_check(ctx, hipGetLastError(), "rlev2_tiled_kernel launch");
 }
@@ -2619,41 +2222,9 @@ int launch_rlev2_tiled(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_
                       value_begin, nvalues, d_dst, dst_bytes, nullptr, 0, d_count);
 }
 
-// Job tables go through a pinned ring mirrored on the device (entries are
-// reused only after the stream has drained: a wrap synchronises first), or
-// into the caller's arena (Ctx::arena_*), which the caller uploads itself.
-int stage_table(Ctx* ctx, const void* src, size_t bytes, const void** out) {
-  const uint64_t need = (bytes + 255) & ~(uint64_t)255;
-  if (ctx->arena_h) {
-    if (ctx->arena_used + need > ctx->arena_cap) return set_error(ctx, ORCG_INVALID_ARGUMENT, "job arena full");
-    memcpy(ctx->arena_h + ctx->arena_used, src, bytes);
-    *out = ctx->arena_d + ctx->arena_used;
-    ctx->arena_used += need;
-    return ORCG_OK;
-  }
-  if (ctx->jobs_cap < need) {
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_jobs) (void)hipFree(ctx->d_jobs);
-    if (ctx->h_jobs) (void)hipHostFree(ctx->h_jobs);
-    ctx->d_jobs = ctx->h_jobs = nullptr;
-    ctx->jobs_cap = ctx->jobs_used = 0;
-    const uint64_t cap = std::max<uint64_t>(4 * need, 256u << 10);
-    int rc = hip_check(ctx, hipMalloc(&ctx->d_jobs, cap), "hipMalloc job table");
-    if (!rc) rc = hip_check(ctx, hipHostMalloc(&ctx->h_jobs, cap, hipHostMallocDefault), "hipHostMalloc job table");
-    if (rc) return rc;
-    ctx->jobs_cap = cap;
-  }
-  if (ctx->jobs_used + need > ctx->jobs_cap) {
-    int rc = hip_check(ctx, hipStreamSynchronize(ctx->stream), "job ring wrap");
-    if (rc) return rc;
-    ctx->jobs_used = 0;
-  }
-  uint8_t* h = (uint8_t*)ctx->h_jobs + ctx->jobs_used;
-  uint8_t* d = (uint8_t*)ctx->d_jobs + ctx->jobs_used;
-  memcpy(h, src, bytes);
-  ctx->jobs_used += need;
-  *out = d;
-  return hip_check(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream), "H2D jobs");
+int launch_rlev2_tiled_jobs(Ctx* ctx, const MultiLaunch& m) {
+  return launch_tiled(ctx, m.variant, nullptr, 0, 0, nullptr, m.grid, false, 0, 0, m.values, nullptr, 8,
+                      (const RleJob*)m.d_jobs, m.njobs, nullptr, &m);
 }
 
 bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 10); }
@@ -2714,112 +2285,6 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     out.push_back(m);
   }
   return ORCG_OK;
-}
-
-// The planned launches, in order. The work before the join runs side by
-// side: the critical RLEv2 instance (the two-pass one, else the one with the
-// most values) on this stream, every other instance on a side lane of its
-// own, and the varint tile counts and RLEv1 segments (kinds 4, 1) on one
-// more lane; then this stream waits for the lanes and runs what reads their
-// outputs (dictionaries, decimals, length scans: kinds 2, 5, 6) itself. The
-// critical path never changes queues: a dependency across HIP queues costs
-// 12-30 us a hop on the MI355X (configs[3] timelines), so the lanes, done
-// long before the critical instance, are the ones waited on, and the
-// post-join kernels follow the critical instance on its own queue.
-int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
-  int ninst = 0, crit = -1;
-  bool aux = false;
-  for (size_t i = 0; i < ls.size(); ++i) {
-    const MultiLaunch& m = ls[i];
-    if (m.kind == 1 || m.kind == 4) aux = true;
-    if (m.kind != 0) continue;
-    ++ninst;
-    const bool two = m.spg > 0, ctwo = crit >= 0 && ls[crit].spg > 0;
-    if (crit < 0 || (two && !ctwo) || (two == ctwo && m.values > ls[crit].values)) crit = (int)i;
-  }
-  const int nlanes = (ninst > 0 ? ninst - 1 : 0) + (aux && ninst > 0 ? 1 : 0);
-  const bool par = nlanes > 0 && side_lanes() > 1 && (size_t)nlanes <= side_lanes() &&
-                   ctx_lane(ctx, (size_t)nlanes - 1) != nullptr;
-  Ctx* const base = ctx;
-  int used = 0, aux_lane = -1, rc = ORCG_OK;
-  if (par) rc = hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "fork event");
-  auto fork = [&](Ctx** c) -> int {  // the next lane, started after the fork point
-    *c = base->lanes[used++];
-    return hip_check(base, hipStreamWaitEvent((*c)->stream, base->ev_fork, 0), "fork wait");
-  };
-  bool joined = false;
-  auto join = [&]() -> int {
-    int r = ORCG_OK;
-    for (int k = 0; k < used; ++k) {
-      int jr = hip_check(base, hipEventRecord(base->ev_join[k], base->lanes[k]->stream), "join event");
-      if (!jr) jr = hip_check(base, hipStreamWaitEvent(base->stream, base->ev_join[k], 0), "join wait");
-      if (jr && !r) r = jr;
-    }
-    joined = true;
-    return r;
-  };
-  for (size_t i = 0; i < ls.size() && !rc; ++i) {
-    const MultiLaunch& m = ls[i];
-    if ((m.kind == 2 || m.kind == 5 || m.kind == 6) && !joined && (rc = join())) break;
-    debug_stale("run_multi: before a launch");
-    if (m.kind == 0) {
-      Ctx* c = base;
-      if (par && (int)i != crit && (rc = fork(&c))) break;
-      // jobs without a record of their own report into the base's (the
-      // lane's own record is the lane's: it frees it)
-      unsigned long long* const own = c->d_err;
-      c->d_err = base->d_err;
-      rc = launch_tiled(c, m.variant, nullptr, 0, 0, nullptr, m.grid, false, 0, 0, m.values, nullptr, 8,
-                        (const RleJob*)m.d_jobs, m.njobs, nullptr, &m);
-      c->d_err = own;
-      if (rc) {
-        char b[160];
-        snprintf(b, sizeof b, " (instance %d, %u streams, %llu segments%s)", m.variant, m.njobs,
-                 (unsigned long long)m.grid, c == base ? "" : ", side lane");
-        base->last_error = c->last_error + b;
-      }
-    } else if (m.kind == 1 || m.kind == 4) {
-      Ctx* c = base;
-      if (par && !joined) {
-        if (aux_lane < 0) {
-          if ((rc = fork(&c))) break;
-          aux_lane = used - 1;
-        }
-        c = base->lanes[aux_lane];
-      }
-      unsigned long long* const own = c->d_err;
-      c->d_err = base->d_err;
-      if (m.kind == 1) {
-        rc = launch_rlev1_jobs(c, (const V1SegDesc*)m.d_jobs, m.grid, m.variant);
-      } else {
-        const VarintJob& J = *(const VarintJob*)m.d_jobs;
-        uint64_t ntiles = 0;
-        rc = launch_varint_tile_counts(c, J.src, J.len, J.counts, &ntiles);
-        if (!rc) rc = launch_exclusive_scan(c, J.counts, ntiles, J.base, nullptr, J.total);
-      }
-      c->d_err = own;
-      if (rc && c != base) base->last_error = c->last_error;
-    } else if (m.kind == 2) {
-      rc = launch_dict_jobs(base, (const DictJob*)m.d_jobs, m.njobs, m.grid);
-    } else if (m.kind == 5) {
-      rc = launch_decimal_jobs(base, (const DecJob*)m.d_jobs, m.njobs, m.grid, m.variant);
-    } else if (m.kind == 6) {
-      const ScanJob& J = *(const ScanJob*)m.d_jobs;
-      rc = launch_exclusive_scan(base, J.in, J.n, J.out, J.flags, J.total);
-    } else {
-      // a pinned single-stream variant: host job (d_jobs is a host pointer)
-      const RleJob& J = *(const RleJob*)m.d_jobs;
-      unsigned long long* const saved = base->d_err;  // the job's own error record
-      if (J.err) base->d_err = J.err;
-      rc = launch_rlev2(base, J.src, J.src_len, (int)J.is_signed, J.segtab, J.nsegs, false, 0, 0, J.nvalues, J.dst, 8);
-      base->d_err = saved;
-    }
-  }
-  if (!joined) {  // join what was forked (also after a failure)
-    const int jr = join();
-    if (jr && !rc) rc = jr;
-  }
-  return rc;
 }
 
 int launch_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs) {

@@ -1,0 +1,134 @@
+#!/usr/bin/env python3
+"""Compare the device assembly of one translation unit between two states of
+the tree: the check for a refactor that must not change the compiled kernels.
+
+    scripts/isa_diff.py rlev2_tiled.hip REV_A [REV_B] [-D MACRO[=V]]... [--by-order]
+
+REV_B defaults to the working tree. For each side, orc_amd/csrc and include/
+are materialised in a temporary directory and the unit is compiled with
+orc_amd/build.py's flags plus `--cuda-device-only -S` (and the -D flags). The
+two assembly files are cut into one piece per function (a kernel's piece
+holds its code and its .amdhsa_* resource directives) and compared as text
+after normalising the `__hip_cuid_<hash>` symbol, which hashes the source.
+--by-order also replaces every function symbol by its ordinal, for changes
+that rename kernels (a template parameter dropped) without changing them.
+
+Prints "identical" or the first differing lines per function; exits 1 on any
+difference. CPU only (a cross-compile); the two compiles run side by side.
+"""
+import argparse
+import importlib.util
+import os
+import re
+import shutil
+import subprocess
+import sys
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DIRS = ["orc_amd/csrc", "include"]
+
+
+def build_settings():
+    spec = importlib.util.spec_from_file_location("_orc_build", os.path.join(ROOT, "orc_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod.HIPCC, mod.ARCH, [f for f in mod.FLAGS if not f.startswith("-D")]
+
+
+def materialise(rev, dst):
+    if rev is None:
+        for d in DIRS:
+            shutil.copytree(os.path.join(ROOT, d), os.path.join(dst, d))
+        return
+    tar = subprocess.run(["git", "-C", ROOT, "archive", rev, "--"] + DIRS, check=True, stdout=subprocess.PIPE).stdout
+    subprocess.run(["tar", "-x", "-C", dst], input=tar, check=True)
+
+
+def compile_asm(rev, tu, defines, workdir):
+    hipcc, arch, flags = build_settings()
+    materialise(rev, workdir)
+    out = os.path.join(workdir, "out.s")
+    cmd = [hipcc, "-x", "hip", "--offload-arch=" + arch] + flags + ["-D" + d for d in defines]
+    cmd += ["--cuda-device-only", "-S", os.path.join(workdir, "orc_amd", "csrc", tu), "-o", out]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if r.returncode != 0:
+        sys.exit("%s: compile failed\n%s" % (rev or "working tree", r.stdout))
+    with open(out) as f:
+        return f.read()
+
+
+FUNC = re.compile(r"^\s*\.type\s+(\S+),@function")
+
+
+def pieces(text, by_order):
+    """[(name, [lines])]: a preamble, one piece per function, the metadata."""
+    text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", text)
+    lines = text.split("\n")
+    names = [m.group(1) for m in map(FUNC.match, lines) if m]
+    if by_order:
+        # longest first: no symbol may be rewritten inside a longer one
+        order = {n: i for i, n in enumerate(names)}
+        pat = re.compile("|".join(re.escape(n) for n in sorted(names, key=len, reverse=True)))
+        if names:
+            lines = [pat.sub(lambda m: "fn#%d" % order[m.group(0)], ln) if "_Z" in ln else ln for ln in lines]
+        names = ["fn#%d" % i for i in range(len(names))]
+    out, cur, k = [], ("(preamble)", []), 0
+    for ln in lines:
+        if FUNC.match(ln):
+            out.append(cur)
+            cur = (names[k], [])
+            k += 1
+        elif ln.lstrip().startswith(".amdgpu_metadata"):
+            out.append(cur)
+            cur = ("(metadata)", [])
+        cur[1].append(ln)
+    out.append(cur)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("tu", help="translation unit under orc_amd/csrc, e.g. rlev2_tiled.hip")
+    ap.add_argument("rev_a")
+    ap.add_argument("rev_b", nargs="?", default=None, help="default: the working tree")
+    ap.add_argument("-D", dest="defines", action="append", default=[], metavar="MACRO[=V]")
+    ap.add_argument("--by-order", action="store_true", help="replace function symbols by their ordinals")
+    ap.add_argument("--context", type=int, default=6, help="differing lines shown per function")
+    args = ap.parse_args()
+
+    with tempfile.TemporaryDirectory(prefix="isa_diff_") as tmp:
+        da, db = os.path.join(tmp, "a"), os.path.join(tmp, "b")
+        os.makedirs(da)
+        os.makedirs(db)
+        with ThreadPoolExecutor(2) as ex:
+            fa = ex.submit(compile_asm, args.rev_a, args.tu, args.defines, da)
+            fb = ex.submit(compile_asm, args.rev_b, args.tu, args.defines, db)
+            ta, tb = fa.result(), fb.result()
+    pa, pb = pieces(ta, args.by_order), pieces(tb, args.by_order)
+    bad = 0
+    if len(pa) != len(pb):
+        print("function count differs: %d vs %d" % (len(pa) - 2, len(pb) - 2))
+        bad += 1
+    kernels = 0
+    for (na, la), (nb, lb) in zip(pa, pb):
+        kernels += any(".amdhsa_kernel" in ln for ln in la)
+        if na == nb and la == lb:
+            print("%s: identical (%d lines)" % (na, len(la)))
+            continue
+        bad += 1
+        if na != nb:
+            print("names differ: %s vs %s" % (na, nb))
+        i = next((i for i, (x, y) in enumerate(zip(la, lb)) if x != y), min(len(la), len(lb)))
+        print("%s: DIFFERS from line %d of %d / %d" % (na, i + 1, len(la), len(lb)))
+        for ln in la[i:i + args.context]:
+            print("  < " + ln)
+        for ln in lb[i:i + args.context]:
+            print("  > " + ln)
+    print("%d kernels, %d pieces compared, %d differ" % (kernels, min(len(pa), len(pb)), bad))
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
