@@ -345,6 +345,52 @@ int orcg_hive11_decimal_decode_device(orcg_ctx* ctx, const uint8_t* d_src, uint6
  * from the trailing-zero code; writer and reader zones with equal rules. */
 int orcg_timestamp_decode_device(orcg_ctx* ctx, int64_t* d_seconds, int64_t* d_nanos, uint64_t n, int64_t epoch);
 
+/* ---- Time zone rules (c++/src/Timezone.hh / Timezone.cc). Host only: none
+ * of the orcg_timezone_* entries touches a GPU. */
+typedef struct orcg_timezone orcg_timezone;
+/* getTimezone(filename, bytes) (Timezone.cc:815-818): TZif v1 / v2+ bytes
+ * (parseZoneFile, :869-946; in a v2+ file the 64-bit block and its POSIX
+ * footer rule, :196-466). A bad file is ORCG_PARSE_ERROR with the reference's
+ * TimezoneError text in orcg_timezone_last_error() ("non-tzfile <name>",
+ * "tzfile too short <name> needs N and has M", "name out of range in variant
+ * ...", "tzfile rule out of range ...", "<what> at <pos> in '<rule>'"). */
+int orcg_timezone_parse(const char* name, const uint8_t* tzif, uint64_t len, orcg_timezone** out);
+/* getTimezoneByName (Timezone.cc:759-810): the US aliases (:47-59), then
+ * <dir>/<name> with <dir> = $TZDIR, else $CONDA_PREFIX/share/zoneinfo, else
+ * /usr/share/zoneinfo (getTimezoneDirectory, :681-695). The UTC names (GMT,
+ * UTC, Etc/UTC, ...) resolve to a built-in zero-offset zone without a file.
+ * A name that is empty, longer than 255 bytes, absolute or has a ".."
+ * component is not opened. Not found: ORCG_INVALID_ARGUMENT. */
+int orcg_timezone_load(const char* name, orcg_timezone** out);
+void orcg_timezone_destroy(orcg_timezone* tz);
+/* Timezone::getVersion (1: 32-bit block, 2: 64-bit block) */
+uint64_t orcg_timezone_version(const orcg_timezone* tz);
+/* Timezone::getEpoch (Timezone.cc:664-679): 2015-01-01 00:00:00 in the zone */
+int64_t orcg_timezone_epoch(const orcg_timezone* tz);
+/* Timezone::getVariant (Timezone.cc:948-963; FutureRuleImpl::getVariant
+ * :275-290 past the last transition). *name is valid until destroy. */
+int orcg_timezone_variant(const orcg_timezone* tz, int64_t clk, int64_t* gmt_offset, int* is_dst, const char** name);
+/* Timezone::convertToUTC / convertFromUTC (Timezone.cc:608-616) */
+int64_t orcg_timezone_convert_to_utc(const orcg_timezone* tz, int64_t clk);
+int64_t orcg_timezone_convert_from_utc(const orcg_timezone* tz, int64_t clk);
+/* this thread's last orcg_timezone_parse / _load failure */
+const char* orcg_timezone_last_error(void);
+/* TimestampColumnReader::next with different writer and reader zones
+ * (c++/src/ColumnReader.cc:318-347), in place: seconds += the writer zone's
+ * epoch, nanos from the trailing-zero code, then the wall-clock adjustment
+ * between the zones' variants (:333-345). Uploads both zones' tables for the
+ * call; the same zone on both sides is orcg_timestamp_decode_device with that
+ * zone's epoch. Synchronous. */
+int orcg_timestamp_decode_tz_device(orcg_ctx* ctx, int64_t* d_seconds, int64_t* d_nanos, uint64_t n,
+                                    const orcg_timezone* writer_tz, const orcg_timezone* reader_tz);
+/* Measurement helper (no reference counterpart): `iters` timed launches over
+ * n values, each on a fresh device copy of d_*_in; ms_out[i] = HIP-event time
+ * of launch i. mode 0: the unadjusted kernel of orcg_timestamp_decode_device
+ * with the writer zone's epoch; 1: the zone-adjusting kernel. */
+int orcg_timestamp_tz_bench(orcg_ctx* ctx, const int64_t* d_seconds_in, const int64_t* d_nanos_in,
+                            int64_t* d_seconds, int64_t* d_nanos, uint64_t n, const orcg_timezone* writer_tz,
+                            const orcg_timezone* reader_tz, int mode, uint32_t iters, double* ms_out);
+
 /* IntegerColumnReader<LongVectorBatch>::next for a whole stripe column
  * (c++/src/ColumnReader.cc:81-104, 224-258): PRESENT (boolean RLE; NULL/0 if
  * the column has no nulls) + DATA (RLEv2) host streams -> not_null[n] and

@@ -37,10 +37,22 @@
  * into blob (StringDictionary::dictionaryOffset); with lazy dictionary
  * decoding (orcg_reader_set_lazy_dictionary, RowReaderOptions::
  * setEnableLazyDecoding) only those are produced (data / length are NULL).
- * Null slots hold 0 (the reference leaves them unspecified). Not decoded
- * (view.decoded == 0): TIMESTAMP columns
- * whose writer time zone is not UTC (the reference converts those with the
- * IANA zone rules, Timezone.cc).
+ * Null slots hold 0 (the reference leaves them unspecified).
+ *
+ * TIMESTAMP columns are adjusted from the stripe's writer zone to the reader
+ * zone (default "GMT") as TimestampColumnReader does (ColumnReader.cc:280-349)
+ * with the IANA rules of both zones (Timezone.cc); a zone resolves through the
+ * rules registered with orcg_reader_set_zone_rules, then the built-in UTC
+ * names, then the zone directory ($TZDIR, else $CONDA_PREFIX/share/zoneinfo,
+ * else /usr/share/zoneinfo). Two deliberate deviations from the reference,
+ * both leaving the column not decoded (view.decoded == 0) with nothing raised:
+ *  - a writer zone whose rules are not found (the reference throws "Time zone
+ *    file ... does not exist");
+ *  - a stripe that names no writer zone (the reference assumes the machine's
+ *    /etc/localtime), unless the caller names the zone with
+ *    orcg_reader_set_local_timezone.
+ * A zone file that is found but malformed fails the read (ORCG_PARSE_ERROR,
+ * the reference's TimezoneError text).
  */
 #ifndef ORCG_READER_H
 #define ORCG_READER_H
@@ -148,6 +160,19 @@ int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on);
  * throw_on_overflow = 1 (the reference's default) is supported. */
 int orcg_reader_set_hive11_decimal(orcg_reader* r, int32_t forced_scale, int throw_on_overflow);
 int32_t orcg_reader_hive11_scale(const orcg_reader* r);
+/* Register the rules of zone `name` (TZif bytes, as orcg_timezone_parse) on
+ * this reader: looked up before the UTC names and the zone directory, under
+ * the name's alias target (US/Pacific = America/Los_Angeles, Timezone.cc:47-59).
+ * For hosts without tzdata. Malformed bytes are reported by the read that
+ * needs the zone. */
+int orcg_reader_set_zone_rules(orcg_reader* r, const char* name, const uint8_t* tzif, uint64_t len);
+/* RowReaderOptions::setTimezoneName (c++/include/orc/Reader.hh:349-354;
+ * default "GMT", Options.hh:170): the zone TIMESTAMP values are read in.
+ * Unknown: ORCG_INVALID_ARGUMENT. TIMESTAMP_INSTANT ignores it. */
+int orcg_reader_set_timezone_name(orcg_reader* r, const char* name);
+/* The writer zone assumed for stripes that name none (NULL / "": none, their
+ * TIMESTAMP columns stay undecoded). Resolved by the reads that need it. */
+int orcg_reader_set_local_timezone(orcg_reader* r, const char* name);
 
 /* Decode one stripe of the selected columns into device batches owned by the
  * reader (valid until the next read or destroy). Synchronous. */
@@ -181,7 +206,8 @@ int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t it
  * instead of 24, and the caller looks each row up in the dictionary
  * (StringDictionaryColumnReader::next, ColumnReader.cc:561-594). A row
  * reader keeps its own
- * RowReaderOptions (include, lazy decoding) and device memory; it borrows
+ * RowReaderOptions (include, lazy decoding, time zone: a copy of the reader's
+ * zones taken at creation) and device memory; it borrows
  * the reader (destroy row readers first), whose decodes it takes turns with. */
 typedef struct orcg_row_reader orcg_row_reader;
 typedef struct {
@@ -189,6 +215,8 @@ typedef struct {
   const uint8_t* include;    /* RowReaderOptions::include by type id (NULL = every column) */
   uint32_t include_len;
   int lazy_dictionary;       /* RowReaderOptions::setEnableLazyDecoding */
+  const char* timezone;      /* RowReaderOptions::setTimezoneName (NULL = the reader's, see
+                                orcg_reader_set_timezone_name); unknown: ORCG_INVALID_ARGUMENT */
 } orcg_row_reader_options;
 /* opts NULL = the whole file, every column */
 int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* opts, orcg_row_reader** out);

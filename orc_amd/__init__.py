@@ -35,7 +35,9 @@ from .rle import (  # noqa: F401
     rlev2_variants,
     scatter_not_null_device,
     timestamp_decode_device,
+    timestamp_decode_tz_device,
 )
+from .timezone import Timezone  # noqa: F401,E402
 
 from .reader import Reader, RowReader, UnionValue, open_reader  # noqa: F401,E402
 

@@ -98,6 +98,19 @@ SIGNATURES = [
     ("orcg_decimal_decode_device", [vp, vp, u64, vp, u64, ctypes.c_uint32, i32, vp], i32),
     ("orcg_hive11_decimal_decode_device", [vp, vp, u64, vp, u64, i32, i32, vp, vp], i32),
     ("orcg_timestamp_decode_device", [vp, vp, vp, u64, ctypes.c_int64], i32),
+    ("orcg_timezone_parse", [cp, cp, u64, ctypes.POINTER(vp)], i32),
+    ("orcg_timezone_load", [cp, ctypes.POINTER(vp)], i32),
+    ("orcg_timezone_destroy", [vp], None),
+    ("orcg_timezone_version", [vp], u64),
+    ("orcg_timezone_epoch", [vp], ctypes.c_int64),
+    ("orcg_timezone_variant", [vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int),
+                               ctypes.POINTER(cp)], i32),
+    ("orcg_timezone_convert_to_utc", [vp, ctypes.c_int64], ctypes.c_int64),
+    ("orcg_timezone_convert_from_utc", [vp, ctypes.c_int64], ctypes.c_int64),
+    ("orcg_timezone_last_error", [], cp),
+    ("orcg_timestamp_decode_tz_device", [vp, vp, vp, u64, vp, vp], i32),
+    ("orcg_timestamp_tz_bench", [vp, vp, vp, vp, vp, u64, vp, vp, i32, ctypes.c_uint32,
+                                 ctypes.POINTER(ctypes.c_double)], i32),
     ("orcg_decode_integer_column", [vp, vp, u64, vp, u64, i32, u64, vp, vp], i32),
     ("orcg_java_last_error", [], cp),
     ("orcg_java_tree_present_next", [vp, vp, u64, vp, ctypes.POINTER(i32), ctypes.POINTER(i32)], i32),
@@ -133,7 +146,7 @@ class ColumnView(ctypes.Structure):
 
 class RowReaderOptions(ctypes.Structure):
     _fields_ = [("offset", u64), ("length", u64), ("include", vp), ("include_len", ctypes.c_uint32),
-                ("lazy_dictionary", i32)]
+                ("lazy_dictionary", i32), ("timezone", cp)]
 
 
 u32 = ctypes.c_uint32
@@ -177,6 +190,9 @@ SIGNATURES += [
     ("orcg_reader_set_lazy_dictionary", [vp, i32], i32),
     ("orcg_reader_set_hive11_decimal", [vp, i32, i32], i32),
     ("orcg_reader_hive11_scale", [vp], i32),
+    ("orcg_reader_set_zone_rules", [vp, cp, cp, u64], i32),
+    ("orcg_reader_set_timezone_name", [vp, cp], i32),
+    ("orcg_reader_set_local_timezone", [vp, cp], i32),
     ("orcg_reader_last_batched_streams", [vp], u64),
     ("orcg_reader_last_stage_bytes", [vp], u64),
     ("orcg_reader_set_stream_batching", [vp, i32], i32),

@@ -536,6 +536,13 @@ class RowReaderOptions {
     tight_ = on;
     return *this;
   }
+  // the zone TIMESTAMP values are read in (c++/include/orc/Reader.hh:349-354;
+  // default "GMT", Options.hh:170)
+  RowReaderOptions& setTimezoneName(const std::string& zoneName) {
+    timezone_ = zoneName;
+    return *this;
+  }
+  const std::string& getTimezoneName() const { return timezone_; }
   bool getUseTightNumericVector() const { return tight_; }
   uint64_t getOffset() const { return offset_; }
   uint64_t getLength() const { return length_; }
@@ -549,6 +556,7 @@ class RowReaderOptions {
   uint64_t offset_ = 0, length_ = std::numeric_limits<uint64_t>::max();
   bool lazy_ = false;
   bool tight_ = false;
+  std::string timezone_ = "GMT";
 };
 
 // orc::ReaderOptions (c++/include/orc/Reader.hh:112-200): the memory pool
@@ -784,6 +792,7 @@ inline RowReader::RowReader(Reader& r, const RowReaderOptions& opts)
   o.offset = opts.getOffset();
   o.length = opts.getLength();
   o.lazy_dictionary = lazy_ ? 1 : 0;
+  o.timezone = opts.getTimezoneName().c_str();
   if (opts.hasInclude()) {
     // RowReaderOptions::include(list<uint64_t>) selects type ids
     const uint32_t nt = orcg_reader_num_types(r.get());
@@ -891,7 +900,7 @@ inline void RowReader::fill(uint32_t id, ColumnVectorBatch& b) {
   orcg_column_view v;
   uint64_t first = 0, n = 0;
   r_.check(orcg_row_reader_column(rr_, id, &v, &first, &n));
-  if (!v.decoded)  // TIMESTAMP of a non-UTC writer zone (include/orcg_reader.h)
+  if (!v.decoded)  // TIMESTAMP whose writer zone's rules were not found (include/orcg_reader.h)
     throw InvalidArgument("column " + std::to_string(id) + " is not decoded by the GPU reader");
   b.numElements = n;
   if (n > b.capacity) b.capacity = n;  // children grow like the reference's resize()

@@ -23,6 +23,7 @@
 // time zone's epoch, nanos (unsigned RLE) with the trailing-zero code in the
 // low 3 bits; writer and reader in the same (or a rule-free) zone.
 #include "orcg_internal.hh"
+#include "timezone.hh"
 
 namespace orcg {
 namespace {
@@ -375,6 +376,128 @@ __global__ __launch_bounds__(256) void timestamp_kernel(int64_t* __restrict__ se
   nanos[i] = nv;
 }
 
+// ---- writer zone != reader zone (ColumnReader.cc:333-345) -------------------
+// A zone's flat table (tz::Zone::device_table, timezone.hh): header, int64
+// trans[n], int32 var[n] (padded to 8 bytes), int64 cycle[1 | 801]; variants
+// packed gmtOffset << 1 | isDst.
+constexpr int kTzThreads = 256;
+constexpr int kTzPer = 4;  // values per thread, 256 apart (coalesced)
+// LDS budget for both tables: 24 KB a workgroup keeps 6 workgroups (24
+// waves) a CU resident in the 160 KB; two "fat" Los_Angeles tables (236
+// transitions each) are 2 x 9.3 KB. Larger pairs are searched in global memory.
+constexpr uint32_t kTzLdsWords = 3072;
+constexpr int64_t kTzCycle = 12622780800LL;  // seconds in 400 years (Timezone.cc:72-75)
+
+struct TzView {
+  const int64_t* trans;
+  const int32_t* var;
+  const int64_t* cycle;
+  uint32_t n, nc;
+  uint64_t w1, w2;  // header words 1 and 2: ancient | standard, dst | startInStd
+  int64_t last;
+  __device__ __forceinline__ int32_t ancient() const { return (int32_t)(uint32_t)w1; }
+  __device__ __forceinline__ int32_t std_v() const { return (int32_t)(uint32_t)(w1 >> 32); }
+  __device__ __forceinline__ int32_t dst_v() const { return (int32_t)(uint32_t)w2; }
+  // the variant of cycle entry idx: even entries are standard time iff startInStd
+  __device__ __forceinline__ int32_t cycle_v(int32_t idx) const {
+    return ((w2 >> 32) != 0) == ((idx & 1) == 0) ? std_v() : dst_v();
+  }
+};
+
+__device__ __forceinline__ TzView tz_view(const int64_t* t) {
+  TzView v;
+  const uint64_t w0 = (uint64_t)t[0];
+  v.n = (uint32_t)w0;
+  v.nc = (uint32_t)(w0 >> 32);
+  v.w1 = (uint64_t)t[1];
+  v.w2 = (uint64_t)t[2];
+  v.last = t[3];
+  v.trans = t + tz::kTableHeaderWords;
+  v.var = (const int32_t*)(v.trans + v.n);
+  v.cycle = v.trans + v.n + (v.n + 1) / 2;
+  return v;
+}
+
+// the last element <= target, or -1: the reference's binarySearch
+// (Timezone.cc:85-113), probe for probe, as tz::search_le on the host
+__device__ __forceinline__ int32_t tz_search(const int64_t* a, uint32_t n, int64_t target) {
+  if (n == 0) return -1;
+  uint32_t lo = 0, hi = n - 1, mid = (lo + hi) / 2;
+  int64_t am = a[mid];
+  while (am != target && lo < hi) {
+    if (am < target) lo = mid + 1;
+    else hi = mid == 0 ? 0 : mid - 1;
+    mid = (lo + hi) / 2;
+    am = a[mid];
+  }
+  return target < am ? (int32_t)mid - 1 : (int32_t)mid;
+}
+
+// clk mod 400 years, floored (FutureRuleImpl::getVariant :279-282); the
+// divisor is a constant, so this is a multiply-high, not a division loop
+__device__ __forceinline__ int64_t tz_cycle_pos(int64_t clk) {
+  int64_t a = clk % kTzCycle;
+  return a < 0 ? a + kTzCycle : a;
+}
+
+// TimezoneImpl::getVariant (:948-963), packed
+__device__ __forceinline__ int32_t tz_variant(const TzView& z, int64_t clk) {
+  if (clk > z.last) {
+    if (z.nc == 1) return z.std_v();
+    return z.cycle_v(tz_search(z.cycle, z.nc, tz_cycle_pos(clk)));
+  }
+  const int32_t i = tz_search(z.trans, z.n, clk);
+  return i < 0 ? z.ancient() : z.var[i];
+}
+
+// the adjustment of one value (ColumnReader.cc:336-344), wrapping sums
+__device__ __forceinline__ int64_t tz_adjust(const TzView& w, const TzView& r, int64_t t) {
+  const int32_t wv = tz_variant(w, t), rv = tz_variant(r, t);
+  if (wv == rv) return t;  // hasSameTzRule: equal gmtOffset and isDst
+  const uint64_t up = (uint64_t)t + (uint64_t)(int64_t)(wv >> 1);
+  const int64_t adj = (int64_t)(up - (uint64_t)(int64_t)(rv >> 1));
+  return (int64_t)(up - (uint64_t)(int64_t)(tz_variant(r, adj) >> 1));
+}
+
+// kLds: both tables staged in LDS (they fit kTzLdsWords), else searched in
+// global memory (L2-resident). Every lane runs its own searches: a form that
+// resolved the wave's first value once and let the lanes inside its ranges
+// share the offsets measured slower on clustered input.
+template <bool kLds>
+__global__ __launch_bounds__(kTzThreads) void timestamp_tz_kernel(int64_t* __restrict__ secs,
+                                                                  int64_t* __restrict__ nanos, uint64_t n,
+                                                                  const int64_t* __restrict__ wtab, uint32_t wwords,
+                                                                  const int64_t* __restrict__ rtab,
+                                                                  uint32_t rwords) {
+  __shared__ int64_t s_tab[kLds ? kTzLdsWords : 1];
+  const int64_t *wt = wtab, *rt = rtab;
+  if constexpr (kLds) {
+    for (uint32_t i = threadIdx.x; i < wwords + rwords; i += kTzThreads)
+      s_tab[i] = i < wwords ? wtab[i] : rtab[i - wwords];
+    __syncthreads();
+    wt = s_tab;
+    rt = s_tab + wwords;
+  }
+  const TzView w = tz_view(wt), r = tz_view(rt);
+  const int64_t epoch = wt[4];
+  const uint64_t base = (uint64_t)blockIdx.x * (kTzThreads * kTzPer) + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kTzPer; ++k) {
+    const uint64_t i = base + (uint64_t)k * kTzThreads;
+    if (i >= n) break;
+    int64_t nv = nanos[i];
+    const uint64_t zeros = (uint64_t)nv & 7u;
+    nv >>= 3;
+    if (zeros != 0)
+      for (uint64_t j = 0; j <= zeros; ++j) nv *= 10;
+    int64_t t = (int64_t)((uint64_t)secs[i] + (uint64_t)epoch);
+    if (t < 0 && nv > 999999) t = (int64_t)((uint64_t)t - 1);
+    t = tz_adjust(w, r, t);
+    secs[i] = t;
+    nanos[i] = nv;
+  }
+}
+
 }  // namespace
 
 int launch_varint_tile_counts(Ctx* ctx, const uint8_t* d_src, uint64_t len, int64_t* d_counts, uint64_t* ntiles) {
@@ -423,6 +546,25 @@ int launch_timestamp(Ctx* ctx, int64_t* d_secs, int64_t* d_nanos, uint64_t n, in
   hipLaunchKernelGGL(timestamp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, d_secs, d_nanos,
                      n, epoch);
   return hip_check(ctx, hipGetLastError(), "timestamp_kernel launch");
+}
+
+int launch_timestamp_tz(Ctx* ctx, int64_t* d_secs, int64_t* d_nanos, uint64_t n, const TzTable& writer,
+                        const TzTable& reader) {
+  if (n == 0) return ORCG_OK;
+  if (!writer.d || !reader.d || writer.words < tz::kTableHeaderWords || reader.words < tz::kTableHeaderWords)
+    return set_error(ctx, ORCG_INVALID_ARGUMENT, "time zone table missing");
+  const uint64_t per = (uint64_t)kTzThreads * kTzPer;
+  const uint64_t blocks = (n + per - 1) / per;
+  if (blocks > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many timestamps for one launch");
+  const bool lds = (uint64_t)writer.words + reader.words <= kTzLdsWords;
+  const dim3 grid((unsigned)blocks), block(kTzThreads);
+  if (lds)
+    hipLaunchKernelGGL(timestamp_tz_kernel<true>, grid, block, 0, ctx->stream, d_secs, d_nanos, n, writer.d,
+                       writer.words, reader.d, reader.words);
+  else
+    hipLaunchKernelGGL(timestamp_tz_kernel<false>, grid, block, 0, ctx->stream, d_secs, d_nanos, n, writer.d,
+                       writer.words, reader.d, reader.words);
+  return hip_check(ctx, hipGetLastError(), "timestamp_tz_kernel launch");
 }
 
 }  // namespace orcg

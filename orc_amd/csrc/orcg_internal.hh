@@ -338,6 +338,15 @@ struct DecJob {
 int launch_decimal_jobs(Ctx* ctx, const DecJob* d_jobs, uint32_t njobs, uint64_t tiles, int mode);
 // TimestampColumnReader value construction, in place.
 int launch_timestamp(Ctx* ctx, int64_t* d_secs, int64_t* d_nanos, uint64_t n, int64_t epoch);
+// A zone's flat table in device memory (tz::Zone::device_table, timezone.hh)
+struct TzTable {
+  const int64_t* d = nullptr;
+  uint32_t words = 0;  // int64 words
+};
+// TimestampColumnReader::next for writer zone != reader zone, in place (the
+// writer zone's epoch is in its table)
+int launch_timestamp_tz(Ctx* ctx, int64_t* d_secs, int64_t* d_nanos, uint64_t n, const TzTable& writer,
+                        const TzTable& reader);
 
 // Row-index segmentation (column_kernels.hip): prefix[g] = non-zero bytes of
 // mask before row rows[g] (counts: scratch of G entries; prefix: G + 1);

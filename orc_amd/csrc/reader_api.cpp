@@ -33,6 +33,7 @@
 #include "../../include/orcg_reader.h"
 #include "orc_file.hh"
 #include "orcg_internal.hh"
+#include "timezone.hh"
 
 using namespace orcg;
 using namespace orcg::file;
@@ -79,19 +80,30 @@ bool is_string_kind(uint32_t k) {
 bool is_int_kind(uint32_t k) {
   return k == ORCG_TYPE_SHORT || k == ORCG_TYPE_INT || k == ORCG_TYPE_LONG || k == ORCG_TYPE_DATE;
 }
-// Zones whose rules are UTC: TIMESTAMP columns written in them decode with
-// no adjustment against the default reader zone, GMT (ColumnReader.cc:333-345
-// is a no-op; epoch 2015-01-01 00:00:00 UTC = 1420070400). Other writer
-// zones need the IANA rules (Timezone.cc) and are not decoded.
-bool utc_zone(const std::string& z) {
-  static const char* kUtc[] = {"GMT", "UTC", "UCT", "Zulu", "Universal", "Greenwich", "GMT0", "GMT+0", "GMT-0",
-                               "Etc/GMT", "Etc/UTC", "Etc/UCT", "Etc/Zulu", "Etc/Universal", "Etc/Greenwich",
-                               "Etc/GMT0", "Etc/GMT+0", "Etc/GMT-0"};
-  for (const char* u : kUtc)
-    if (z == u) return true;
-  return false;
-}
-constexpr int64_t kOrcEpochUtc = 1420070400;
+// Zones whose rules are UTC (tz::is_utc_name): TIMESTAMP columns written in
+// them decode with no adjustment against the default reader zone, GMT
+// (ColumnReader.cc:333-345 is a no-op; epoch 2015-01-01 00:00:00 UTC =
+// 1420070400), and no zone file is read for them. Every other zone resolves,
+// per stripe, through the rules registered on the reader
+// (orcg_reader_set_zone_rules), then the IANA directory (tz::load_zone_file);
+// writer and reader zone then differ and the values are adjusted on the
+// device (timestamp_tz_kernel).
+bool utc_zone(const std::string& z) { return tz::is_utc_name(z); }
+constexpr int64_t kOrcEpochUtc = tz::kOrcEpochUtc;
+
+// A zone a reader resolved: its rules (or, for a zone file that was found but
+// is malformed, the TimezoneError text) and, after the first decode that
+// needs it, its flat table in device memory (the reader's own allocation,
+// uploaded once).
+struct ZoneEntry {
+  std::unique_ptr<tz::Zone> zone;
+  std::string err;
+  int64_t* d_tab = nullptr;
+  uint32_t words = 0;
+  ~ZoneEntry() {
+    if (d_tab) (void)hipFree(d_tab);
+  }
+};
 
 // [off, off + len) lies inside [0, end), written so that no sum can wrap
 // (offsets and lengths come from the file and are untrusted)
@@ -99,12 +111,14 @@ bool range_ok(uint64_t off, uint64_t len, uint64_t end) { return off <= end && l
 
 // Columns this reader decodes: every primitive, list / map / struct / union,
 // decimals (Hive 0.11 precision-0 decimals at the forced scale), timestamps
-// of UTC writers.
-bool is_supported(const file::TypeInfo& t, const std::string& writer_tz) {
+// whose stripe's writer zone resolved (writer_zone; NULL: the zone's rules
+// were not found, or the stripe names no zone and the caller named none with
+// orcg_reader_set_local_timezone, and the column stays undecoded).
+bool is_supported(const file::TypeInfo& t, const ZoneEntry* writer_zone) {
   const uint32_t k = t.kind;
   if (k == ORCG_TYPE_UNION) return true;
   if (k == ORCG_TYPE_DECIMAL) return true;
-  if (k == ORCG_TYPE_TIMESTAMP) return utc_zone(writer_tz);
+  if (k == ORCG_TYPE_TIMESTAMP) return writer_zone != nullptr;
   if (k == ORCG_TYPE_TIMESTAMP_INSTANT) return true;
   return k <= ORCG_TYPE_CHAR || k == ORCG_TYPE_DATE || k == ORCG_TYPE_VARCHAR;
 }
@@ -185,6 +199,10 @@ struct Col {
   uint64_t blob_len = 0;
   uint64_t dict_size = 0;  // ColumnEncoding.dictionarySize of this stripe
   bool supported = false;  // decoded by this reader (is_supported for this stripe's writer zone)
+  // a stream of this column whose compression chunks do not parse: raised
+  // when the decode reaches the column, as the reference reads streams
+  // column by column (an earlier column's error comes first)
+  std::string stream_err;
   int64_t* secondary = nullptr;  // TIMESTAMP nanoseconds
   uint8_t* tags = nullptr;       // UNION: child of each row (UnionVectorBatch::tags)
   int64_t* index = nullptr;      // dictionary strings: entry of each row (EncodedStringVectorBatch::index)
@@ -214,6 +232,7 @@ int slot_of(uint32_t stream_kind) {
 // staging, run plans and their segment tables appended (no device work).
 struct HostStage {
   uint64_t stripe = ~0ull;
+  const ZoneEntry* writer_zone = nullptr;  // the stripe's resolved writer zone (TIMESTAMP columns)
   std::vector<Col> cols;  // streams (and, while decoding, the outputs)
   uint8_t* h = nullptr;   // pinned staging
   size_t cap = 0;
@@ -310,12 +329,31 @@ struct orcg_reader {
   Ctx* ctx = nullptr;
   std::vector<uint8_t> selected;
   bool lazy_dict = false;
+  // Time zones (RowReaderOptions::setTimezoneName, default "GMT"; the zone
+  // assumed for stripes that name none): the reader's own, and those of the
+  // decode in progress. Resolved zones live as long as the reader (zones,
+  // under tz_mu: prepare() resolves writer zones on worker threads).
+  const ZoneEntry* own_reader_tz = nullptr;  // nullptr: the built-in UTC zone
+  std::string own_local_tz;
+  const ZoneEntry* reader_tz = nullptr;
+  std::string local_tz;
+  mutable std::mutex tz_mu;
+  mutable std::map<std::string, std::unique_ptr<ZoneEntry>> zones;  // by canonical name
+  mutable std::vector<std::unique_ptr<ZoneEntry>> zones_replaced;   // entries set_zone_rules replaced
+  mutable std::unique_ptr<ZoneEntry> utc_entry;
+  const ZoneEntry* utc_zone_entry() const;                       // caller holds tz_mu
+  const ZoneEntry* resolve_zone(const std::string& name) const;  // NULL: not found
+  int zone_table(const ZoneEntry* z, TzTable* out);
   struct Active {
     orcg_reader* r;
-    Active(orcg_reader* r_, Ctx* c, const std::vector<uint8_t>& sel, bool lazy) : r(r_) {
+    Active(orcg_reader* r_, Ctx* c, const std::vector<uint8_t>& sel, bool lazy, const ZoneEntry* rtz,
+           const std::string& ltz)
+        : r(r_) {
       r->ctx = c;
       r->selected = sel;
       r->lazy_dict = lazy;
+      r->reader_tz = rtz ? rtz : r->resolve_zone("GMT");
+      r->local_tz = ltz;
     }
     ~Active() { r->ctx = nullptr; }
   };
@@ -587,8 +625,8 @@ struct orcg_reader {
   int open_tail();
   // (sel: the column selection of the read it prepares for; prepare reads
   // nothing else the decodes change, so it runs without mu)
-  int prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel) const;
-  int prepare(uint64_t s, HostStage& hs) const { return prepare(s, hs, selected); }
+  int prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel, const std::string& local_zone) const;
+  int prepare(uint64_t s, HostStage& hs) const { return prepare(s, hs, selected, local_tz); }
   int read_stripes(uint64_t first, uint64_t count);
   int upload_and_decode(HostStage& hs, DevSlot& ds);  // issue + finish
   void issue(HostStage& hs, DevSlot& ds, Flight& fl);
@@ -1182,6 +1220,7 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
   ctx->d_err = D->d_errs + id;
   c.n = n;
   c.decoded = true;
+  if (!c.stream_err.empty()) return fail(ORCG_PARSE_ERROR, c.stream_err);
   int rc;
   cur_rows = rg_rows;
   cur_n = n;
@@ -1362,7 +1401,19 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
     int64_t *secs, *nanos;
     if ((rc = int_stream(c, kSlotData, true, nonnull, &secs, false, d_nonnull))) return rc;
     if ((rc = int_stream(c, kSlotSecondary, false, nonnull, &nanos, false, d_nonnull))) return rc;
-    if ((rc = launch_timestamp(ctx, secs, nanos, nonnull, kOrcEpochUtc))) return fail_ctx(rc);
+    // TIMESTAMP_INSTANT ignores both zones; the same zone on both sides is
+    // sameTimezone_ (:286): no adjustment, with that zone's epoch
+    const ZoneEntry* wz = k == ORCG_TYPE_TIMESTAMP ? H->writer_zone : nullptr;
+    if (wz && !reader_tz) return fail(ORCG_INVALID_ARGUMENT, "reader time zone not found");
+    if (wz && !reader_tz->zone) return fail(ORCG_PARSE_ERROR, reader_tz->err);
+    if (!wz || wz == reader_tz) {
+      if ((rc = launch_timestamp(ctx, secs, nanos, nonnull, wz ? wz->zone->epoch() : kOrcEpochUtc)))
+        return fail_ctx(rc);
+    } else {
+      TzTable wt, rt;
+      if ((rc = zone_table(wz, &wt)) || (rc = zone_table(reader_tz, &rt))) return rc;
+      if ((rc = launch_timestamp_tz(ctx, secs, nanos, nonnull, wt, rt))) return fail_ctx(rc);
+    }
     if (!(c.data = place_i64(secs)) || !(c.secondary = place_i64(nanos))) return fail_ctx(ORCG_DEVICE_ERROR);
   } else if (is_int_kind(k)) {
     if (!has_data) return fail(ORCG_PARSE_ERROR, "DATA stream not found in Integer column");
@@ -1829,7 +1880,55 @@ static bool long_runs(const uint8_t* p, uint64_t len) {
   return runs > 0 && pos >= 96 * runs;
 }
 
-int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& selected) const {
+const ZoneEntry* orcg_reader::utc_zone_entry() const {
+  if (!utc_entry) {
+    utc_entry.reset(new ZoneEntry());
+    utc_entry->zone = tz::Zone::utc("GMT");
+  }
+  return utc_entry.get();
+}
+
+// registered rules, then the built-in UTC names, then the zone directory
+const ZoneEntry* orcg_reader::resolve_zone(const std::string& name) const {
+  const std::string canon = tz::canonical_name(name);
+  std::lock_guard<std::mutex> lk(tz_mu);
+  auto it = zones.find(canon);
+  if (it != zones.end()) return it->second.get();
+  if (tz::is_utc_name(canon)) return utc_zone_entry();
+  std::unique_ptr<ZoneEntry> e(new ZoneEntry());
+  try {
+    if (!tz::load_zone_file(canon, &e->zone)) return nullptr;  // looked up again by the next read
+  } catch (const tz::TimezoneError& x) {
+    e->err = x.what();
+  }
+  return (zones[canon] = std::move(e)).get();
+}
+
+// the zone's device table, uploaded at its first use (synchronous copy)
+int orcg_reader::zone_table(const ZoneEntry* cz, TzTable* out) {
+  ZoneEntry* z = const_cast<ZoneEntry*>(cz);  // decodes are serialised by mu
+  if (!z->d_tab) {
+    const std::vector<int64_t> t = z->zone->device_table();
+    int64_t* d = nullptr;
+    if (hipMalloc((void**)&d, t.size() * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(ORCG_OUT_OF_MEMORY, "time zone table allocation failed");
+    }
+    if (hipMemcpy(d, t.data(), t.size() * 8, hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(d);
+      return fail(ORCG_DEVICE_ERROR, "H2D of the time zone table failed");
+    }
+    z->d_tab = d;
+    z->words = (uint32_t)t.size();
+  }
+  out->d = z->d_tab;
+  out->words = z->words;
+  return ORCG_OK;
+}
+
+int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& selected,
+                         const std::string& local_zone) const {
   hs.stripe = s;
   hs.rc = ORCG_OK;
   hs.err.clear();
@@ -1861,11 +1960,25 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
                                          std::to_string(nt) + ", actual=" + std::to_string(sf.encodings.size()));
   hs.cols = std::vector<Col>(nt);
   hs.slack = upload_tail_bytes(nt, 0, (si.num_rows + 2047) / 2048 + 1);
+  // The stripe's writer zone (StripeFooter.writerTimezone; the reference
+  // assumes the machine's /etc/localtime for a stripe that names none, here
+  // the caller names it or the column stays undecoded), resolved only when a
+  // TIMESTAMP column is read. Not found: undecoded, nothing raised (the
+  // reference throws); found but malformed: the TimezoneError.
+  hs.writer_zone = nullptr;
+  for (size_t i = 0; i < nt && !hs.writer_zone; ++i) {
+    if (footer.types[i].kind != ORCG_TYPE_TIMESTAMP || !selected[i]) continue;
+    const std::string& zn = sf.writer_timezone.empty() ? local_zone : sf.writer_timezone;
+    if (zn.empty()) break;
+    hs.writer_zone = resolve_zone(zn);
+    if (!hs.writer_zone) break;
+    if (!hs.writer_zone->zone) return hs.fail(ORCG_PARSE_ERROR, hs.writer_zone->err);
+  }
   for (size_t i = 0; i < nt; ++i) {
     hs.cols[i].kind = footer.types[i].kind;
     hs.cols[i].encoding = sf.encodings[i].kind;
     hs.cols[i].dict_size = sf.encodings[i].dictionary_size;
-    hs.cols[i].supported = is_supported(footer.types[i], sf.writer_timezone);
+    hs.cols[i].supported = is_supported(footer.types[i], hs.writer_zone);
   }
   struct Need {
     uint32_t col;
@@ -1888,7 +2001,10 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
       return hs.fail(ORCG_PARSE_ERROR, "Malformed stream meta at stream index " + std::to_string(i) + " in stripe " +
                                            std::to_string(s));
     Need nd{st.column, slot, {}, st.offset};
-    if (!split_chunks(file, st.offset, st.length, ps.compression, nd.chunks, err)) return hs.fail(ORCG_PARSE_ERROR, err);
+    if (!split_chunks(file, st.offset, st.length, ps.compression, nd.chunks, err)) {
+      if (hs.cols[st.column].stream_err.empty()) hs.cols[st.column].stream_err = err;
+      continue;
+    }
     needs.push_back(std::move(nd));
   }
   // I/O (ReaderMetrics::IOCount / IOBlockingLatencyUs): the reference preads
@@ -2725,6 +2841,8 @@ struct orcg_row_reader {
   // this row reader's RowReaderOptions
   std::vector<uint8_t> selected;
   bool lazy_dict = false;
+  const ZoneEntry* reader_tz = nullptr;  // setTimezoneName (nullptr: GMT)
+  std::string local_tz;                  // the zone of stripes that name none
   uint64_t nstripes = 0, first = 0, last = 0;  // stripes [first, last) are in range
   uint64_t current = 0, row_in_stripe = 0, rows_in_stripe = 0;
   uint64_t previous_row = 0;
@@ -2883,7 +3001,7 @@ struct orcg_row_reader {
         prepared[u & 1] = u;
         ahead = std::thread([this, u] {
           const double tp = now_s();
-          (void)r->prepare(u, stage[u & 1], selected);  // a failure is kept in the stage
+          (void)r->prepare(u, stage[u & 1], selected, local_tz);  // a failure is kept in the stage
           addp(4, now_s() - tp);
         });
       }
@@ -2891,7 +3009,7 @@ struct orcg_row_reader {
     if (prepared[t & 1] == t) start_ahead();
     {
       std::lock_guard<std::mutex> lk(r->mu);
-      orcg_reader::Active act(r, own, selected, lazy_dict);
+      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz);
       (void)hipSetDevice(r->ctx->device);
       rc = ORCG_OK;
       if (prepared[t & 1] != t) {
@@ -3109,6 +3227,40 @@ int orcg_reader_set_hive11_decimal(orcg_reader* r, int32_t forced_scale, int thr
   return ORCG_OK;
 }
 int32_t orcg_reader_hive11_scale(const orcg_reader* r) { return r ? r->hive11_scale : 6; }
+
+int orcg_reader_set_zone_rules(orcg_reader* r, const char* name, const uint8_t* tzif, uint64_t len) {
+  if (!r || !name || !*name || (len && !tzif)) return ORCG_INVALID_ARGUMENT;
+  std::unique_ptr<ZoneEntry> e(new ZoneEntry());
+  const std::string canon = tz::canonical_name(name);
+  try {
+    e->zone = tz::Zone::parse(canon, tzif, len);
+  } catch (const tz::TimezoneError& x) {
+    e->err = x.what();  // raised by the read that needs the zone
+  }
+  std::lock_guard<std::mutex> lk(r->mu);  // no decode holds the old entry
+  std::lock_guard<std::mutex> lz(r->tz_mu);
+  std::unique_ptr<ZoneEntry>& slot = r->zones[canon];
+  if (slot) r->zones_replaced.push_back(std::move(slot));  // a row reader may still name it
+  slot = std::move(e);
+  return ORCG_OK;
+}
+
+int orcg_reader_set_timezone_name(orcg_reader* r, const char* name) {
+  if (!r || !name) return ORCG_INVALID_ARGUMENT;
+  const ZoneEntry* z = r->resolve_zone(name);
+  if (!z) return r->fail_user(ORCG_INVALID_ARGUMENT, std::string("Time zone ") + name + " not found");
+  if (!z->zone) return r->fail_user(ORCG_PARSE_ERROR, z->err);
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->own_reader_tz = z;
+  return ORCG_OK;
+}
+
+int orcg_reader_set_local_timezone(orcg_reader* r, const char* name) {
+  if (!r) return ORCG_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->own_local_tz = name ? name : "";
+  return ORCG_OK;
+}
 int orcg_reader_format_version(const orcg_reader* r, uint32_t* major, uint32_t* minor) {
   if (!r || !major || !minor) return ORCG_INVALID_ARGUMENT;
   // the reference reports 0.11 when the version is absent (FileVersion::v_0_11)
@@ -3204,14 +3356,14 @@ int orcg_reader_read_stripe(orcg_reader* r, uint64_t stripe) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
   return r->read_stripes(stripe, 1);
 }
 
 int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t iters, double* decode_s, double* h2d_s) {
   if (!r || !decode_s || !h2d_s || iters == 0) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
   if (!r->ctx) return r->fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (stripe >= r->footer.stripes.size()) return r->fail(ORCG_INVALID_ARGUMENT, "stripe index out of range");
   hipSetDevice(r->ctx->device);
@@ -3233,7 +3385,7 @@ int orcg_reader_read_stripes(orcg_reader* r, uint64_t first, uint64_t count) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
   return r->read_stripes(first, count);
 }
 
@@ -3286,6 +3438,19 @@ int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* o, orc
   int rc = compute_selection(r, o ? o->include : nullptr, o && o->include ? o->include_len : 0, rr->selected);
   if (rc) return rc;
   rr->lazy_dict = o && o->lazy_dictionary != 0;
+  {
+    // its own copy of the reader's zones; opts->timezone replaces the reader zone
+    std::lock_guard<std::mutex> lk(r->mu);
+    rr->reader_tz = r->own_reader_tz;
+    rr->local_tz = r->own_local_tz;
+  }
+  if (o && o->timezone) {
+    const ZoneEntry* z = r->resolve_zone(o->timezone);
+    if (!z || !z->zone)
+      return r->fail_user(z ? ORCG_PARSE_ERROR : ORCG_INVALID_ARGUMENT,
+                          z ? z->err : std::string("Time zone ") + o->timezone + " not found");
+    rr->reader_tz = z;
+  }
   rr->node = current_numa_node();
   if ((rc = orcg_ctx_create(r->own_ctx->device, &rr->own)) != ORCG_OK)
     return r->fail_user(rc, "row reader context creation failed");

@@ -421,16 +421,35 @@ class Reader:
     def hive11_scale(self):
         return int(self._L.orcg_reader_hive11_scale(self._h))
 
+    def set_zone_rules(self, name, tzif):
+        """Register zone `name`'s rules (TZif bytes) on this reader: used
+        before the zone directory ($TZDIR), e.g. on hosts without tzdata."""
+        tzif = bytes(tzif)
+        check(self._L.orcg_reader_set_zone_rules(self._h, name.encode(), tzif, len(tzif)), self._err)
+
+    def set_timezone(self, name):
+        """RowReaderOptions::setTimezoneName (default "GMT"): the zone
+        TIMESTAMP values are read in; InvalidArgument for an unknown zone."""
+        check(self._L.orcg_reader_set_timezone_name(self._h, name.encode()), self._err)
+
+    def set_local_timezone(self, name):
+        """The writer zone of stripes that name none (None: such stripes'
+        TIMESTAMP columns stay undecoded; the reference assumes the machine's
+        /etc/localtime)."""
+        check(self._L.orcg_reader_set_local_timezone(self._h, None if name is None else name.encode()), self._err)
+
     def set_lazy_dictionary(self, on=True):
         """RowReaderOptions::setEnableLazyDecoding for stripe reads."""
         check(self._L.orcg_reader_set_lazy_dictionary(self._h, int(bool(on))), self._err)
 
-    def create_row_reader(self, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False):
+    def create_row_reader(self, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False,
+                          timezone=None):
         """Reader::createRowReader(RowReaderOptions): `include` type ids (or
         top-level field names), range(offset, length) in file bytes,
-        setEnableLazyDecoding, setUseTightNumericVector."""
+        setEnableLazyDecoding, setUseTightNumericVector, setTimezoneName
+        (None: the reader's zone, set_timezone)."""
         return RowReader(self, include=include, offset=offset, length=length, lazy_dictionary=lazy_dictionary,
-                         tight_numeric=tight_numeric)
+                         tight_numeric=tight_numeric, timezone=timezone)
 
     def last_timings(self):
         t = (ctypes.c_double * 5)()
@@ -506,7 +525,8 @@ class RowReader:
     seek_to_row follow RowReaderImpl (:424-499); range(offset, length)
     selects the stripes whose offset falls in the byte range (:337-345)."""
 
-    def __init__(self, reader, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False):
+    def __init__(self, reader, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False,
+                 timezone=None):
         if reader._ctx is None:
             raise _lib.InvalidArgument("reader was opened without a device context")
         self.reader = reader
@@ -523,6 +543,7 @@ class RowReader:
             opts.include = self._inc.ctypes.data_as(ctypes.c_void_p)
             opts.include_len = self._inc.size
         opts.lazy_dictionary = int(bool(lazy_dictionary))
+        opts.timezone = None if timezone is None else timezone.encode()
         h = ctypes.c_void_p()
         check(self._L.orcg_row_reader_create(reader._h, ctypes.byref(opts), ctypes.byref(h)), reader._err)
         self._h = h

@@ -498,6 +498,18 @@ def timestamp_decode_device(ctx, seconds, nanos, epoch=1420070400):
     return seconds, nanos
 
 
+def timestamp_decode_tz_device(ctx, seconds, nanos, writer_tz, reader_tz):
+    """TimestampColumnReader value construction with different writer and
+    reader zones (orc_amd.Timezone), on device tensors, in place: raw seconds
+    relative to the ORC epoch + encoded nanos -> seconds / nanoseconds in the
+    reader zone (c++/src/ColumnReader.cc:318-347)."""
+    L = _lib.load()
+    ctx.after_torch()
+    check(L.orcg_timestamp_decode_tz_device(ctx.handle, _tensor_ptr(seconds), _tensor_ptr(nanos), seconds.numel(),
+                                            writer_tz.handle, reader_tz.handle), ctx.last_error)
+    return seconds, nanos
+
+
 def decode_integer_column(present, data, n, is_signed=True, ctx=None):
     """IntegerColumnReader::next over a stripe column: (values, not_null);
     null slots of `values` stay 0 (untouched)."""
