@@ -34,6 +34,8 @@ SUPPORTED = {BOOLEAN, BYTE, SHORT, INT, LONG, FLOAT, DOUBLE, STRING, BINARY, LIS
              CHAR, UNION}
 STRING_KINDS = (STRING, VARCHAR, CHAR, BINARY)
 _EPOCH = datetime.date(1970, 1, 1)
+# scaleb rounds to the context's precision (28 digits by default): an Int128 has up to 39
+_DECIMAL_CTX = decimal.Context(prec=40)
 
 
 class UnionValue(tuple):
@@ -124,7 +126,7 @@ class Batch:
                 u = (hi << 64) | lo
             else:
                 u = int(c.data[i])
-            return decimal.Decimal(u).scaleb(-(c.scale if c.scale is not None else t.scale))
+            return decimal.Decimal(u).scaleb(-(c.scale if c.scale is not None else t.scale), _DECIMAL_CTX)
         if k in (TIMESTAMP, TIMESTAMP_INSTANT):
             # TimestampVectorBatch seconds + nanoseconds, as numpy datetime64[ns]
             return np.datetime64(int(c.data[i]) * 1_000_000_000 + int(c.secondary[i]), "ns")

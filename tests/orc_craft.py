@@ -39,6 +39,11 @@ def type_msg(kind, subtypes=(), names=()):
     return m
 
 
+def decimal_type(precision, scale):
+    """Type{kind = DECIMAL, precision = 5, scale = 6} (precision 0: Hive 0.11)."""
+    return type_msg(T_DECIMAL) + field_varint(5, precision) + field_varint(6, scale)
+
+
 def orc_file(body, stripes, types, num_rows, footer_length_override=None, row_index_stride=None):
     """'ORC' + body + Footer + PostScript + 1-byte PostScript length
     (uncompressed). row_index_stride: Footer.rowIndexStride (field 8), left
@@ -58,7 +63,7 @@ def orc_file(body, stripes, types, num_rows, footer_length_override=None, row_in
 # Footer", "Type Information")
 PRESENT, DATA, LENGTH, DICTIONARY_DATA, SECONDARY, ROW_INDEX = 0, 1, 2, 3, 5, 6
 ENC_DIRECT, ENC_DICTIONARY, ENC_DIRECT_V2, ENC_DICTIONARY_V2 = 0, 1, 2, 3
-T_SHORT, T_INT, T_LONG, T_STRING, T_STRUCT = 2, 3, 4, 7, 12
+T_SHORT, T_INT, T_LONG, T_STRING, T_STRUCT, T_DECIMAL = 2, 3, 4, 7, 12, 14
 
 
 def stream_msg(kind, column, length):
@@ -67,6 +72,19 @@ def stream_msg(kind, column, length):
 
 def encoding_msg(kind, dictionary_size=None):
     return field_varint(1, kind) + (b"" if dictionary_size is None else field_varint(2, dictionary_size))
+
+
+def bool_rle(bits):
+    """A PRESENT stream: bits MSB first into bytes, byte RLE as literal groups
+    of at most 128 bytes (ORCv1.md "Boolean Run Length Encoding")."""
+    padded = list(bits) + [0] * (-len(bits) % 8)
+    by = bytes(sum(int(b) << (7 - j) for j, b in enumerate(padded[i:i + 8])) for i in range(0, len(padded), 8))
+    out = bytearray()
+    for i in range(0, len(by), 128):
+        chunk = by[i:i + 128]
+        out.append(256 - len(chunk))
+        out += chunk
+    return bytes(out)
 
 
 def row_index_msg(entries):
@@ -119,9 +137,10 @@ def struct_stripe(columns, row_index=True):
 
 
 def struct_file(names, kinds, stripes, row_index_stride):
-    """An uncompressed file of struct<names[i]: kinds[i]> (Type.Kind numbers)
-    with any number of stripes = [(num_rows, [CraftColumn per column])]. A
-    row_index_stride of 0 writes no index section."""
+    """An uncompressed file of struct<names[i]: kinds[i]> (Type.Kind numbers,
+    or whole Type messages as bytes: decimal_type) with any number of stripes
+    = [(num_rows, [CraftColumn per column])]. A row_index_stride of 0 writes
+    no index section."""
     body, infos, total = b"", [], 0
     for num_rows, columns in stripes:
         assert len(columns) == len(names)
@@ -129,5 +148,6 @@ def struct_file(names, kinds, stripes, row_index_stride):
         infos.append(stripe_info(3 + len(body), len(index), len(data), len(sf), num_rows))
         body += index + data + sf
         total += num_rows
-    types = [type_msg(T_STRUCT, list(range(1, len(names) + 1)), names)] + [type_msg(k) for k in kinds]
+    types = [type_msg(T_STRUCT, list(range(1, len(names) + 1)), names)]
+    types += [k if isinstance(k, bytes) else type_msg(k) for k in kinds]
     return orc_file(body, infos, types, total, row_index_stride=row_index_stride)
