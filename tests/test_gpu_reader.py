@@ -329,7 +329,7 @@ def test_first_error_in_column_order(ctx):
     """Two corrupt columns in one stripe: the error reported is the first
     column's (the reference decodes a batch column by column, StructColumnReader
     ::next), although the second column's bad value comes earlier in row
-    order: every column has its own device error record (reader_api.cpp
+    order: every column has its own device error record (reader_stripes.cpp
     first_error). pyarrow's ORC C++ reader raises the same error on the
     same file."""
     ok = orc_amd.Reader(_two_column_file(None, None), ctx).read_stripe(0).to_pylist()
