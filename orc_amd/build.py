@@ -21,7 +21,7 @@ SOURCES = ["rlev2_kernels.hip", "rlev2_tiled.hip", "rlev2_expand.hip", "byterle_
            "row_reader.cpp", "byterle_api.cpp", "decimal_api.cpp", "timezone.cpp", "encoder.cpp", "java_face.cpp"]
 if PROF or AB:
     SOURCES.append("probe_kernels.hip")
-HEADERS = ["orcg_internal.hh", "rlev2_device.hh", "orc_file.hh", "timezone.hh", "reader_layout.hh", "reader_internal.hh", os.path.join("..", "..", "include", "orcg.h"),
+HEADERS = ["orcg_internal.hh", "device_util.hh", "rlev2_device.hh", "orc_file.hh", "timezone.hh", "reader_layout.hh", "reader_internal.hh", os.path.join("..", "..", "include", "orcg.h"),
            os.path.join("..", "..", "include", "orcg_reader.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

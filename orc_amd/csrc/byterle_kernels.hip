@@ -14,7 +14,8 @@
 // block hops, a workgroup scan: byterle_kernel below) and the decoded bytes
 // are assembled a dword per lane through an owner map, stored coalesced.
 // In boolean mode every decoded byte becomes 8 output rows (chars 0/1).
-#include "rlev2_device.hh"
+#include "device_util.hh"
+#include "orcg_internal.hh"
 
 namespace orcg {
 namespace {
@@ -145,25 +146,16 @@ __global__ __launch_bounds__(kBThreads) void byterle_kernel(const uint8_t* __res
   const uint64_t end = begin + (d_nout ? *d_nout : nout);
   const uint64_t scale = kBool ? 8 : 1;  // output units per decoded byte
   const uint64_t vend = (end + scale - 1) / scale;  // decoded bytes needed: index < vend
-  const uint64_t seg_start = segtab[2 * g];
-  uint64_t vi = segtab[2 * g + 1];
-  uint64_t seg_end = src_len, v_next = ~0ull;
-  if (g + 1 < nsegs) {
-    seg_end = segtab[2 * (g + 1)];
-    v_next = segtab[2 * (g + 1) + 1];
-  }
-  if (seg_end > src_len) seg_end = src_len;
+  Seg sg;
+  seg_lookup<false>(segtab, nsegs, g, src_len, sg);
+  const uint64_t seg_start = sg.seg_start, seg_end = sg.seg_end, v_next = sg.v_next;
+  uint64_t vi = sg.vi;
   if (vi * scale >= end || (v_next != ~0ull && v_next * scale <= begin)) return;  // nothing to decode
 
-  // range-checked descriptor over [seg_start & ~15, end of stream): loads
-  // past the stream return zeros
-  const uintptr_t base_abs = ((uintptr_t)src + seg_start) & ~(uintptr_t)15;
-  const uintptr_t end_abs = ((uintptr_t)src + src_len + 3) & ~(uintptr_t)3;
-  const uint64_t span = (uint64_t)(end_abs - base_abs);
-  const uint32_t nrec = span > 0xfffff000ull ? 0xfffff000u : (uint32_t)span;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)base_abs, (short)0, (int)nrec, 0x00020000);
-  const uint64_t bias = (uint64_t)(base_abs - (uintptr_t)src);
+  StreamDesc sd;
+  stream_desc(src, src_len, seg_start, sd);
+  const __amdgpu_buffer_rsrc_t rs = sd.rs;
+  const uint64_t bias = sd.bias;
 
   uint32_t ones = 0;  // set rows this thread wrote (boolean mode)
   bool stopped = false;
@@ -415,7 +407,7 @@ __global__ __launch_bounds__(kBThreads) void byterle_kernel(const uint8_t* __res
     vi += dec_total;
   }
   if (kBool && ones_total) {
-    for (int m = 32; m >= 1; m >>= 1) ones += (uint32_t)__shfl_xor((int)ones, m);
+    ones = wave_sum(ones);
     if (lane == 0 && ones) atomicAdd(ones_total, (unsigned long long)ones);
   }
   BPROF_MARK(7);

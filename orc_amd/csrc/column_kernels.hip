@@ -9,7 +9,8 @@
 //  * dictionary gather: index -> (blob offset, length) with the reference's
 //    bounds check (StringDictionaryColumnReader::next, c++/src/
 //    ColumnReader.cc:561-594).
-#include "rlev2_device.hh"
+#include "device_util.hh"
+#include "orcg_internal.hh"
 
 namespace orcg {
 namespace {
@@ -102,10 +103,7 @@ __device__ uint64_t lb_lookback(unsigned long long* status, uint32_t t, uint32_t
     }
     const uint64_t pm = __ballot(fl == 2);
     const int first = pm ? __builtin_ctzll(pm) : kWave;
-    uint64_t c = (k >= 0 && lane <= first) ? v : 0ull;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    excl += c;
+    excl += wave_sum<uint64_t>((k >= 0 && lane <= first) ? v : 0ull);
     if (pm) break;
   }
   return excl;
@@ -136,28 +134,69 @@ __global__ __launch_bounds__(kThreads) void tile_count_kernel(const uint8_t* __r
   }
 }
 
-// Exclusive scan of `n` uint32 counts into uint64 offsets, one workgroup.
-__global__ __launch_bounds__(1024) void scan_kernel(const uint32_t* __restrict__ counts, uint64_t n,
-                                                     uint64_t* __restrict__ offsets) {
+// The one-workgroup exclusive scan: `n` values of Tin into offsets[0 .. n]
+// (Tout; offsets[n] = the total, sums wrapping mod 2^64), 1,024 values a trip
+// with the carry in LDS. What else it reports:
+//  * kScanCounts: nothing (tile counts -> tile offsets, uint32 -> uint64);
+//  * kScanDict: dictionary entry lengths -> offsets (int64). With `aux`:
+//    aux[0] = the blob bytes (offsets[n]), aux[1] = 1 if an entry length is
+//    negative (loadStringDictionary's check, DictionaryLoader.cc:71-77), both
+//    stored -- the file reader's whole dictionary preparation in one launch;
+//  * kScanFlags: uint64 -> uint64. With `aux`: the negative / wrap flags
+//    OR-ed into aux[0], aux[1] (strlen_flags above); with `total`: *total =
+//    offsets[n].
+enum ScanReport { kScanCounts, kScanDict, kScanFlags };
+
+template <typename Tin, typename Tout, int kReport>
+__global__ __launch_bounds__(1024) void wg_scan_kernel(const Tin* __restrict__ in, uint64_t n,
+                                                        Tout* __restrict__ offsets,
+                                                        unsigned long long* __restrict__ aux,
+                                                        uint64_t* __restrict__ total) {
   __shared__ uint64_t wsum[1024 / kWave];
   __shared__ uint64_t carry_s;
+  __shared__ uint32_t neg_s;  // kScanDict
   const int lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
-  if (threadIdx.x == 0) carry_s = 0;
+  if (threadIdx.x == 0) {
+    carry_s = 0;
+    if constexpr (kReport == kScanDict) neg_s = 0;
+  }
   __syncthreads();
+  bool neg = false, wrap = false;
   for (uint64_t b = 0; b < n; b += 1024) {
     const uint64_t i = b + threadIdx.x;
-    const uint64_t x = i < n ? counts[i] : 0;
-    const uint64_t inc = wave_inclusive_scan(x, lane);
+    const uint64_t x = i < n ? (uint64_t)in[i] : 0;  // (0 past n: neither negative nor a wrap)
+    const uint64_t inc = wave_inclusive_scan(x);
     if (lane == kWave - 1) wsum[wv] = inc;
     __syncthreads();
     uint64_t before = carry_s;
     for (int w = 0; w < wv; ++w) before += wsum[w];
-    if (i < n) offsets[i] = before + inc - x;
+    const uint64_t st = before + inc - x;
+    if (i < n) offsets[i] = (Tout)st;
+    if constexpr (kReport != kScanCounts) neg |= (int64_t)x < 0;
+    if constexpr (kReport == kScanFlags) wrap |= st + x < st;
     __syncthreads();
     if (threadIdx.x == 1023) carry_s = before + inc;
     __syncthreads();
   }
-  if (threadIdx.x == 0) offsets[n] = carry_s;
+  if constexpr (kReport == kScanDict) {
+    if (aux && __any(neg) && lane == 0) atomicOr(&neg_s, 1u);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    offsets[n] = (Tout)carry_s;
+    if constexpr (kReport == kScanDict) {
+      if (aux) {
+        aux[0] = carry_s;
+        aux[1] = neg_s;
+      }
+    }
+    if constexpr (kReport == kScanFlags) {
+      if (total) *total = carry_s;
+    }
+  }
+  if constexpr (kReport == kScanFlags) {
+    if (aux) strlen_flags(aux, neg, wrap);
+  }
 }
 
 // One workgroup per kTile rows; row r = tile + 256 k + tid (k < 16), so the
@@ -222,48 +261,6 @@ __global__ void dict_gather_kernel(const T* __restrict__ idx, const uint8_t* __r
     const int64_t s = offsets[e];
     out_start[i] = s;
     out_len[i] = offsets[e + 1] - s;
-  }
-}
-
-// Dictionary offsets: exclusive scan of the entry lengths (one workgroup).
-// With `summary`: [0] = the blob bytes (offsets[n]), [1] = 1 if an entry
-// length is negative (loadStringDictionary's check, DictionaryLoader.cc:71-77)
-// -- the file reader's whole dictionary preparation in one launch.
-__global__ __launch_bounds__(1024) void lengths_scan_kernel(const int64_t* __restrict__ lengths, uint64_t n,
-                                                             int64_t* __restrict__ offsets,
-                                                             uint64_t* __restrict__ summary) {
-  __shared__ uint64_t wsum[1024 / kWave];
-  __shared__ uint64_t carry_s;
-  __shared__ uint32_t neg_s;
-  const int lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
-  if (threadIdx.x == 0) {
-    carry_s = 0;
-    neg_s = 0;
-  }
-  __syncthreads();
-  bool neg = false;
-  for (uint64_t b = 0; b < n; b += 1024) {
-    const uint64_t i = b + threadIdx.x;
-    const uint64_t x = i < n ? (uint64_t)lengths[i] : 0;
-    neg |= (int64_t)x < 0;
-    const uint64_t inc = wave_inclusive_scan(x, lane);
-    if (lane == kWave - 1) wsum[wv] = inc;
-    __syncthreads();
-    uint64_t before = carry_s;
-    for (int w = 0; w < wv; ++w) before += wsum[w];
-    if (i < n) offsets[i] = (int64_t)(before + inc - x);
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + inc;
-    __syncthreads();
-  }
-  if (summary && __any(neg) && lane == 0) atomicOr(&neg_s, 1u);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    offsets[n] = (int64_t)carry_s;
-    if (summary) {
-      summary[0] = carry_s;
-      summary[1] = neg_s;
-    }
   }
 }
 
@@ -374,44 +371,9 @@ __global__ __launch_bounds__(kThreads) void dict_multi_kernel(const DictJob* __r
 // Exclusive scans of int64 values (lengths -> offsets): direct string
 // lengths (DATA offsets, StringDirectColumnReader::next, c++/src/
 // ColumnReader.cc:725-793) and list/map lengths (ListColumnReader::
-// nextInternal, :960-993), one workgroup below 8,192 values, else the
-// single-pass look-back kernel over 4,096-value tiles.
+// nextInternal, :960-993), one workgroup (wg_scan_kernel) up to 8,192 values,
+// else the single-pass look-back kernel over 4,096-value tiles.
 constexpr int kScanTile = 4096;  // 256 threads x 16 values
-
-// Exclusive scan of `n` uint64 into `offsets` (n + 1 entries), one workgroup.
-// (flags, may be null: strlen_flags below)
-__global__ __launch_bounds__(1024) void scan64_kernel(const uint64_t* __restrict__ in, uint64_t n,
-                                                       uint64_t* __restrict__ offsets,
-                                                       unsigned long long* __restrict__ flags = nullptr,
-                                                       uint64_t* __restrict__ total = nullptr) {
-  __shared__ uint64_t wsum[1024 / kWave];
-  __shared__ uint64_t carry_s;
-  const int lane = threadIdx.x % kWave, wv = threadIdx.x / kWave;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  bool neg = false, wrap = false;
-  for (uint64_t b = 0; b < n; b += 1024) {
-    const uint64_t i = b + threadIdx.x;
-    const uint64_t x = i < n ? in[i] : 0;
-    const uint64_t inc = wave_inclusive_scan(x);
-    if (lane == kWave - 1) wsum[wv] = inc;
-    __syncthreads();
-    uint64_t before = carry_s;
-    for (int w = 0; w < wv; ++w) before += wsum[w];
-    const uint64_t st = before + inc - x;
-    if (i < n) offsets[i] = st;
-    neg |= i < n && (int64_t)x < 0;
-    wrap |= i < n && st + x < st;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = before + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    offsets[n] = carry_s;
-    if (total) *total = carry_s;
-  }
-  if (flags) strlen_flags(flags, neg, wrap);
-}
 
 // Single-pass exclusive scan (decoupled look-back): workgroup tickets in
 // dispatch order (an atomic on status[ntiles]); a tile's 4,096 values are
@@ -715,27 +677,38 @@ struct alignas(16) Pair128 {
   __host__ __device__ explicit Pair128(int64_t f) : hi(f < 0 ? -1 : 0), lo(f) {}
 };
 
+// Tile counts of the not-null bytes (scratch slot 5), then their exclusive
+// scan (slot 6: tiles + 1 offsets, the last one the total).
+static int launch_tile_offsets(Ctx* ctx, const uint8_t* d_nn, uint64_t n, uint64_t tiles, uint64_t** d_off) {
+  if (tiles > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many rows");
+  void *d_counts, *off;
+  int rc = scratch(ctx, 5, tiles * sizeof(uint32_t), &d_counts);
+  if (!rc) rc = scratch(ctx, 6, (tiles + 1) * sizeof(uint64_t), &off);
+  if (rc) return rc;
+  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, d_nn, n,
+                     (uint32_t*)d_counts);
+  hipLaunchKernelGGL((wg_scan_kernel<uint32_t, uint64_t, kScanCounts>), dim3(1), dim3(1024), 0, ctx->stream,
+                     (const uint32_t*)d_counts, tiles, (uint64_t*)off, (unsigned long long*)nullptr,
+                     (uint64_t*)nullptr);
+  *d_off = (uint64_t*)off;
+  return ORCG_OK;
+}
+
 int launch_scatter(Ctx* ctx, const void* d_dense, const uint8_t* d_nn, uint64_t n, void* d_out, int width,
                    int fill_mode, int64_t fill) {
   if (n == 0) return ORCG_OK;
   const uint64_t tiles = (n + kTile - 1) / kTile;
-  if (tiles > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many rows");
-  void *d_counts, *d_off;
-  int rc = scratch(ctx, 5, tiles * sizeof(uint32_t), &d_counts);
-  if (!rc) rc = scratch(ctx, 6, (tiles + 1) * sizeof(uint64_t), &d_off);
+  uint64_t* d_off;
+  const int rc = launch_tile_offsets(ctx, d_nn, n, tiles, &d_off);
   if (rc) return rc;
-  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, d_nn, n,
-                     (uint32_t*)d_counts);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_counts, tiles,
-                     (uint64_t*)d_off);
 #define ORCG_SC(T)                                                                                     \
   do {                                                                                                 \
     if (fill_mode)                                                                                     \
       hipLaunchKernelGGL((scatter_kernel<T, true>), dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, \
-                         (const T*)d_dense, d_nn, n, (const uint64_t*)d_off, (T*)d_out, (T)fill);      \
+                         (const T*)d_dense, d_nn, n, d_off, (T*)d_out, (T)fill);      \
     else                                                                                               \
       hipLaunchKernelGGL((scatter_kernel<T, false>), dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, \
-                         (const T*)d_dense, d_nn, n, (const uint64_t*)d_off, (T*)d_out, (T)fill);      \
+                         (const T*)d_dense, d_nn, n, d_off, (T*)d_out, (T)fill);      \
   } while (0)
   switch (width) {
     case 16: ORCG_SC(Pair128); break;
@@ -751,8 +724,8 @@ int launch_scatter(Ctx* ctx, const void* d_dense, const uint8_t* d_nn, uint64_t 
 
 int launch_dict_offsets(Ctx* ctx, const int64_t* d_lengths, uint64_t dict_size, int64_t* d_offsets,
                         uint64_t* d_summary) {
-  hipLaunchKernelGGL(lengths_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, d_lengths, dict_size, d_offsets,
-                     d_summary);
+  hipLaunchKernelGGL((wg_scan_kernel<int64_t, int64_t, kScanDict>), dim3(1), dim3(1024), 0, ctx->stream, d_lengths,
+                     dict_size, d_offsets, (unsigned long long*)d_summary, (uint64_t*)nullptr);
   return hip_check(ctx, hipGetLastError(), "dictionary offsets launch");
 }
 
@@ -817,8 +790,8 @@ int launch_exclusive_scan(Ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_
   unsigned long long* const fl = (unsigned long long*)d_flags;
   if (n <= 8192) {
     // short inputs (varint tile counts, dictionary lengths): one workgroup
-    hipLaunchKernelGGL(scan64_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint64_t*)d_in, n, (uint64_t*)d_out,
-                       fl, d_total);
+    hipLaunchKernelGGL((wg_scan_kernel<uint64_t, uint64_t, kScanFlags>), dim3(1), dim3(1024), 0, ctx->stream,
+                       (const uint64_t*)d_in, n, (uint64_t*)d_out, fl, d_total);
     return hip_check(ctx, hipGetLastError(), "scan launch");
   }
   const uint64_t tiles = (n + kScanTile - 1) / kScanTile;
@@ -835,16 +808,10 @@ int launch_exclusive_scan(Ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_
 int launch_count_nonzero(Ctx* ctx, const uint8_t* d_nn, uint64_t n, uint64_t* d_total) {
   if (n == 0) return hip_check(ctx, hipMemsetAsync(d_total, 0, sizeof(uint64_t), ctx->stream), "count memset");
   const uint64_t tiles = (n + kTile - 1) / kTile;
-  if (tiles > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many rows");
-  void *d_counts, *d_off;
-  int rc = scratch(ctx, 5, tiles * sizeof(uint32_t), &d_counts);
-  if (!rc) rc = scratch(ctx, 6, (tiles + 1) * sizeof(uint64_t), &d_off);
+  uint64_t* d_off;
+  int rc = launch_tile_offsets(ctx, d_nn, n, tiles, &d_off);
   if (rc) return rc;
-  hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, d_nn, n,
-                     (uint32_t*)d_counts);
-  hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const uint32_t*)d_counts, tiles,
-                     (uint64_t*)d_off);
-  rc = hip_check(ctx, hipMemcpyAsync(d_total, (uint64_t*)d_off + tiles, sizeof(uint64_t), hipMemcpyDeviceToDevice,
+  rc = hip_check(ctx, hipMemcpyAsync(d_total, d_off + tiles, sizeof(uint64_t), hipMemcpyDeviceToDevice,
                                      ctx->stream), "count copy");
   return rc ? rc : hip_check(ctx, hipGetLastError(), "count launch");
 }

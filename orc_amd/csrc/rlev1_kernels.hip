@@ -14,7 +14,8 @@
 // lane's hop over at most 32 block entries (rlev1_kernel below). Round 4's
 // kernel was one wavefront walking every header and 64-byte literal slice
 // through global loads: 52 us per 5,000-value stream of configs[0].
-#include "rlev2_device.hh"
+#include "device_util.hh"
+#include "orcg_internal.hh"
 
 namespace orcg {
 namespace {
@@ -107,37 +108,15 @@ __device__ __forceinline__ bool slow_varint(__amdgpu_buffer_rsrc_t rs, uint64_t 
   return true;
 }
 
-// The segment of launch-wide index gg: its stream and segment bounds.
-struct V1Seg {
+// The segment of launch-wide index gg: its stream and (Seg) segment bounds.
+struct V1Seg : Seg {
   const uint8_t* src;
   uint64_t src_len;
   int is_signed;
   void* dst;
   unsigned long long* err;
   uint64_t begin, end;  // output value range
-  uint64_t seg_start, vi, seg_end, v_next;
 };
-
-// segtab: {byte offset, first value index} per segment, or (jobs) the job's
-// table / row-index triplets, as rlev2_tiled_kernel's multi-stream instances
-// read them (value index = rows[g] - skip, clamped at 0, rg_segtab_kernel).
-__device__ __forceinline__ void seg_bounds(const uint64_t* segtab, const int64_t* trip, const int64_t* rows,
-                                           uint64_t nsegs, uint64_t g, uint64_t src_len, V1Seg& s) {
-  auto at = [&](uint64_t k, uint64_t* off) -> uint64_t {
-    if (trip) {
-      const int64_t v = rows[k] - trip[3 * k + 1];
-      *off = (uint64_t)trip[3 * k];
-      return v < 0 ? 0ull : (uint64_t)v;
-    }
-    *off = segtab[2 * k];
-    return segtab[2 * k + 1];
-  };
-  s.vi = at(g, &s.seg_start);
-  s.seg_end = src_len;
-  s.v_next = ~0ull;
-  if (g + 1 < nsegs) s.v_next = at(g + 1, &s.seg_end);
-  if (s.seg_end > src_len) s.seg_end = src_len;
-}
 
 // One workgroup per segment; kCB bytes per thread (16: 4 KB windows for
 // long segments, e.g. a row group; 4: 1 KB windows for the short segments of
@@ -236,7 +215,7 @@ __global__ __launch_bounds__(kV1Threads) void rlev1_kernel(const uint8_t* __rest
       S.err = p_err;
       S.begin = value_begin;
       S.end = value_begin + nvalues;
-      seg_bounds(p_segtab, nullptr, nullptr, p_nsegs, gg, p_src_len, S);
+      seg_lookup<false>(p_segtab, p_nsegs, gg, p_src_len, S);
     }
   }
   T* const dst = (T*)S.dst;
@@ -250,15 +229,10 @@ __global__ __launch_bounds__(kV1Threads) void rlev1_kernel(const uint8_t* __rest
     return;
   }
 
-  // range-checked descriptor over [seg_start & ~15, end of stream): loads
-  // past the stream return zeros
-  const uintptr_t base_abs = ((uintptr_t)S.src + S.seg_start) & ~(uintptr_t)15;
-  const uintptr_t end_abs = ((uintptr_t)S.src + S.src_len + 3) & ~(uintptr_t)3;
-  const uint64_t span = (uint64_t)(end_abs - base_abs);
-  const uint32_t nrec = span > 0xfffff000ull ? 0xfffff000u : (uint32_t)span;
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc((void*)base_abs, (short)0, (int)nrec, 0x00020000);
-  const uint64_t bias = (uint64_t)(base_abs - (uintptr_t)S.src);
+  StreamDesc sd;
+  stream_desc(S.src, S.src_len, S.seg_start, sd);
+  const __amdgpu_buffer_rsrc_t rs = sd.rs;
+  const uint64_t bias = sd.bias;
   const int sg = S.is_signed;
 
   V1PROF_MARK(0);

@@ -1,7 +1,9 @@
 // Device helpers shared by the RLEv2 kernels: width tables, the big-endian
-// bit-field extract, wavefront scans and the run-header parser.
+// bit-field extract and the run-header parser (the scans, the descriptor and
+// the segment lookup every decoder shares are device_util.hh).
 #pragma once
 
+#include "device_util.hh"
 #include "orcg_internal.hh"
 
 namespace orcg {
@@ -9,7 +11,6 @@ namespace dev {
 
 typedef uint32_t u32x3 __attribute__((ext_vector_type(3)));
 
-constexpr int kWave = 64;
 constexpr int kMaxRunUnroll = 8;  // 512 values / 64 lanes
 
 // FBSToBitWidthMap (c++/src/RLEV2Util.cc:24-26)
@@ -33,22 +34,6 @@ __device__ __forceinline__ uint32_t closest_fixed_bits(uint32_t n) {
   return 64;
 }
 
-// unZigZag (c++/src/RLE.hh:32-34)
-__device__ __forceinline__ uint64_t unzigzag(uint64_t v) { return (v >> 1) ^ (0 - (v & 1)); }
-
-// Values the wave agrees on but the compiler cannot prove uniform (loaded
-// from LDS or computed from such loads): readfirstlane puts them in SGPRs, so
-// the code that depends on them stays scalar (a v_readlane with a VGPR lane
-// index becomes a waterfall loop).
-__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
-__device__ __forceinline__ uint64_t uni64(uint64_t x) {
-  return ((uint64_t)uni((uint32_t)(x >> 32)) << 32) | uni((uint32_t)x);
-}
-
-__device__ __forceinline__ uint32_t rdlane(uint32_t v, uint32_t lane) {
-  return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)lane);
-}
-
 // The W-bit big-endian field starting `sh` bits into byte `rel`, given the
 // three little-endian dwords at (rel & ~3). W in 1..64, W + sh <= 64 for
 // every width the format can produce (non byte-multiple widths are <= 30).
@@ -58,56 +43,6 @@ __device__ __forceinline__ uint64_t field(u32x3 w, uint32_t rel, uint32_t sh, ui
   const uint32_t hi = __builtin_amdgcn_alignbyte(w.z, w.y, r);
   const uint64_t be = ((uint64_t)__builtin_bswap32(lo) << 32) | __builtin_bswap32(hi);
   return (be << sh) >> (64 - W);
-}
-
-// Wavefront inclusive prefix sums on DPP (no LDS round trips): Kogge-Stone
-// inside each 16-lane row with row_shr:1,2,4,8, then row_bcast:15 (rows 1,3)
-// and row_bcast:31 (rows 2,3) carry the row totals across. Requires all 64
-// lanes active. Invalid source lanes read 0 (bound_ctrl).
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ uint32_t dpp0(uint32_t x) {
-  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, kCtrl, kRowMask, 0xf, true);
-}
-
-__device__ __forceinline__ uint32_t wave_scan_u32(uint32_t x) {
-  x += dpp0<0x111, 0xf>(x);  // row_shr:1
-  x += dpp0<0x112, 0xf>(x);  // row_shr:2
-  x += dpp0<0x114, 0xf>(x);  // row_shr:4
-  x += dpp0<0x118, 0xf>(x);  // row_shr:8
-  x += dpp0<0x142, 0xa>(x);  // row_bcast:15
-  x += dpp0<0x143, 0xc>(x);  // row_bcast:31
-  return x;
-}
-
-template <int kCtrl, int kRowMask>
-__device__ __forceinline__ uint64_t dpp0_64(uint64_t x) {
-  const uint32_t lo = dpp0<kCtrl, kRowMask>((uint32_t)x), hi = dpp0<kCtrl, kRowMask>((uint32_t)(x >> 32));
-  return ((uint64_t)hi << 32) | lo;
-}
-
-__device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t x, int /*lane*/ = 0) {
-  x += dpp0_64<0x111, 0xf>(x);
-  x += dpp0_64<0x112, 0xf>(x);
-  x += dpp0_64<0x114, 0xf>(x);
-  x += dpp0_64<0x118, 0xf>(x);
-  x += dpp0_64<0x142, 0xa>(x);
-  x += dpp0_64<0x143, 0xc>(x);
-  return x;
-}
-
-// Value of lane 63 (wave-uniform, scalar register).
-__device__ __forceinline__ uint64_t last_lane(uint64_t x) {
-  return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(x >> 32), 63) << 32) |
-         (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, 63);
-}
-
-__device__ __forceinline__ void report(unsigned long long* err, uint64_t value_index, uint32_t code) {
-  atomicMin(err, (unsigned long long)((value_index << 8) | code));
-}
-
-template <typename T>
-__device__ __forceinline__ void put(T* dst, uint64_t idx, uint64_t v) {
-  dst[idx] = (T)(int64_t)v;
 }
 
 // A parsed run header (RleDecoderV2::next* header logic, RleDecoderV2.cc:

@@ -8,8 +8,10 @@ REV_B defaults to the working tree. For each side, orc_amd/csrc and include/
 are materialised in a temporary directory and the unit is compiled with
 orc_amd/build.py's flags plus `--cuda-device-only -S` (and the -D flags). The
 two assembly files are cut into one piece per function (a kernel's piece
-holds its code and its .amdhsa_* resource directives) and compared as text
-after normalising the `__hip_cuid_<hash>` symbol, which hashes the source.
+holds its code and its .amdhsa_* resource directives), paired by name and
+compared as text after normalising the `__hip_cuid_<hash>` symbol, which
+hashes the source, and the function ordinals in local labels; a function on
+one side only is listed.
 --by-order also replaces every function symbol by its ordinal, for changes
 that rename kernels (a template parameter dropped) without changing them.
 
@@ -60,11 +62,17 @@ def compile_asm(rev, tu, defines, workdir):
 
 
 FUNC = re.compile(r"^\s*\.type\s+(\S+),@function")
+HEAD = re.compile(r"^\s*\.(section|text|globl|protected|hidden|weak|p2align)\b")
 
 
 def pieces(text, by_order):
     """[(name, [lines])]: a preamble, one piece per function, the metadata."""
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", text)
+    # local labels carry their function's ordinal (.LBB12_3, .Lfunc_end12):
+    # dropped, so that a function compares equal wherever it stands in the unit
+    text = re.sub(r"\.(LBB|Lfunc_begin|Lfunc_end|LJTI|LCPI)\d+", r".\1", text)
+    text = re.sub(r"\bBB\d+_", "BB_", text)  # (the loop comments' block names)
+    text = re.sub(r"[ \t]+;", " ;", text)  # (comments are aligned after the label, whose length changed)
     lines = text.split("\n")
     names = [m.group(1) for m in map(FUNC.match, lines) if m]
     if by_order:
@@ -77,8 +85,13 @@ def pieces(text, by_order):
     out, cur, k = [], ("(preamble)", []), 0
     for ln in lines:
         if FUNC.match(ln):
+            # the directives that open the function (.section, .globl, ...)
+            # stand before its .type line: they name it, so they go with it
+            head = []
+            while cur[1] and HEAD.match(cur[1][-1]):
+                head.insert(0, cur[1].pop())
             out.append(cur)
-            cur = (names[k], [])
+            cur = (names[k], head)
             k += 1
         elif ln.lstrip().startswith(".amdgpu_metadata"):
             out.append(cur)
@@ -108,7 +121,22 @@ def main():
             ta, tb = fa.result(), fb.result()
     pa, pb = pieces(ta, args.by_order), pieces(tb, args.by_order)
     bad = 0
-    if len(pa) != len(pb):
+    if not args.by_order:
+        # pair the pieces by name (a change may reorder the functions, e.g.
+        # a kernel that became a template instance); the rest are listed
+        na, nb = [n for n, _ in pa], [n for n, _ in pb]
+        for n in na:
+            if n not in nb:
+                print("%s: only in %s" % (n, args.rev_a))
+                bad += 1
+        for n in nb:
+            if n not in na:
+                print("%s: only in %s" % (n, args.rev_b or "the working tree"))
+                bad += 1
+        db_ = dict(pb)
+        pa = [(n, l) for n, l in pa if n in db_]
+        pb = [(n, db_[n]) for n, _ in pa]
+    elif len(pa) != len(pb):
         print("function count differs: %d vs %d" % (len(pa) - 2, len(pb) - 2))
         bad += 1
     kernels = 0

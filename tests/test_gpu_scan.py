@@ -2,7 +2,8 @@
 ListColumnReader::nextInternal, c++/src/ColumnReader.cc:960-993; direct string
 lengths -> starts, :725-793): the single-pass decoupled look-back kernel
 against numpy at tile edges and large sizes (4,096 values a tile), and the
-one-workgroup path below 8,192 values."""
+one-workgroup kernel (up to 8,192 values; also the dictionary offsets and the
+null scatter's tile offsets) at the edges of its 1,024-value trips."""
 import ctypes
 
 import numpy as np
@@ -13,7 +14,8 @@ import orc_amd
 pytestmark = pytest.mark.gpu
 
 
-@pytest.mark.parametrize("n", [0, 1, 4095, 8192, 8193, 4096 * 3, 4096 * 3 + 1, 1_000_003, 2_634_752])
+@pytest.mark.parametrize("n", [0, 1, 63, 64, 1023, 1024, 1025, 2049, 4095, 8191, 8192, 8193, 4096 * 3, 4096 * 3 + 1,
+                               1_000_003, 2_634_752])
 def test_exclusive_scan_matches_numpy(n):
     import torch
 
@@ -67,6 +69,56 @@ def test_exclusive_scan_exact_for_any_int64(big):
     with np.errstate(over="ignore"):
         want = np.concatenate([[0], np.cumsum(x)]).astype(np.int64)
     np.testing.assert_array_equal(_scan(ctx, x), want)
+
+
+@pytest.mark.parametrize("n,neg_at", [(1, None), (1023, None), (1024, None), (1025, None), (3000, None), (3000, 1500)])
+def test_dict_offsets_trip_edges(n, neg_at):
+    """Dictionary entry lengths -> offsets through the one-workgroup scan, at
+    dictionary sizes around its 1,024-entry trip; a negative length in the
+    second trip still gives numpy's wrapping cumsum (the reader reports it
+    from the kernel's summary: the reader tests cover that)."""
+    import torch
+
+    ctx = orc_amd.Context(0)
+    rng = np.random.default_rng(n)
+    x = rng.integers(0, 1 << 20, size=n, dtype=np.int64)
+    if n > 10:
+        x[rng.integers(0, min(n, 1024), size=2)] = 1 << 40  # carried out of the first trip
+    if neg_at is not None:
+        x[neg_at] = -(1 << 33) - 7
+    d_off = torch.full((n + 1,), -1, dtype=torch.int64, device="cuda")
+    orc_amd.dict_offsets_device(ctx, torch.from_numpy(x).cuda(), d_off)
+    ctx.synchronize()
+    want = np.concatenate([[0], np.cumsum(x)]).astype(np.int64)
+    np.testing.assert_array_equal(d_off.cpu().numpy(), want)
+
+
+@pytest.mark.parametrize("tiles", [1, 1024, 1025, 2049])
+def test_scatter_tile_offset_trip_edges(tiles):
+    """The null scatter's tile offsets are the one-workgroup scan of its
+    4,096-row tile counts: exactly 1, 1,024, 1,025 and 2,049 tiles (the last
+    tile of the latter two holding one row), int16 values, about 60 % of the
+    rows not null, with and without the fill."""
+    import torch
+
+    n = 4096 * tiles if tiles in (1, 1024) else 4096 * tiles - 4095
+    assert (n + 4095) // 4096 == tiles
+    rng = np.random.default_rng(tiles)
+    nn = (rng.random(n) < 0.6).astype(np.uint8)
+    dense = rng.integers(-100, 100, size=int(nn.sum())).astype(np.int16)
+    ctx = orc_amd.Context(0)
+    sentinel = np.full(n, 55, dtype=np.int16)
+    out = torch.from_numpy(sentinel.copy()).cuda()
+    d_dense, d_nn = torch.from_numpy(dense).cuda(), torch.from_numpy(nn).cuda()
+    orc_amd.scatter_not_null_device(ctx, d_dense, d_nn, out)
+    ctx.synchronize()
+    want = sentinel.copy()
+    want[nn == 1] = dense
+    np.testing.assert_array_equal(out.cpu().numpy(), want)
+    orc_amd.scatter_not_null_device(ctx, d_dense, d_nn, out, fill=1)
+    ctx.synchronize()
+    want[nn == 0] = 1
+    np.testing.assert_array_equal(out.cpu().numpy(), want)
 
 
 def test_exclusive_scan_epoch_wrap():
