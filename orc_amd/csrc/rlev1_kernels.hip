@@ -619,7 +619,8 @@ __global__ __launch_bounds__(kV1Threads) void rlev1_kernel(const uint8_t* __rest
           for (uint32_t j = 0; j < k; ++j) {
             uint64_t u;
             if (!slow_varint(rs, bias, q, S.src_len, u)) {
-              if (lane == 0) report(S.err, vi, kErrV1BadRead);
+              // (only a requested value reports: the reference reads no further)
+              if (lane == 0 && vi < vend) report(S.err, vi, kErrV1BadRead);
               bad = true;
               break;
             }

@@ -18,6 +18,16 @@ def _varint(u, out):
             return
 
 
+def _padded(u, nbytes, out):
+    """u as a varint of exactly nbytes bytes, the payload first (continuation
+    bytes past the value's own carry zeros: legal for readLong, which reads
+    until a byte below 0x80 and drops bits past 64)."""
+    u &= (1 << 64) - 1
+    for i in range(nbytes):
+        b = (u >> (7 * i)) & 0x7F if 7 * i < 64 else 0
+        out.append(b | (0x80 if i + 1 < nbytes else 0))
+
+
 def _zz(v):
     v &= (1 << 64) - 1
     s = v >> 63
@@ -25,16 +35,20 @@ def _zz(v):
 
 
 def encode(groups, signed):
-    """groups: list of ("run", base, delta, length) or ("lit", [values])."""
+    """groups: list of ("run", base, delta, length), ("run", base, delta,
+    length, nbytes) with the base padded to nbytes bytes, or ("lit", [values])."""
     out = bytearray()
     values = []
     for g in groups:
         if g[0] == "run":
-            _, base, delta, length = g
+            _, base, delta, length = g[:4]
             assert 3 <= length <= 130 and -128 <= delta <= 127
             out.append(length - 3)
             out.append(delta & 0xFF)
-            _varint(_zz(base) if signed else base, out)
+            if len(g) > 4:
+                _padded(_zz(base) if signed else base, g[4], out)
+            else:
+                _varint(_zz(base) if signed else base, out)
             for i in range(length):
                 v = (base + i * delta) & ((1 << 64) - 1)
                 values.append(v - (1 << 64) if v >> 63 else v)

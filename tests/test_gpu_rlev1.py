@@ -9,6 +9,7 @@ import pytest
 import orc_amd
 from conftest import load_golden
 from oracle import oracle
+from rlev1_model import decode as model_decode, padded_varint
 from rlev1_writer import encode, random_groups
 
 pytestmark = pytest.mark.gpu
@@ -100,17 +101,6 @@ def test_rlev1_truncated_stream_raises_reference_error(ctx):
     np.testing.assert_array_equal(got, vals[:10])
 
 
-def _padded_varint(u, nbytes):
-    """A base-128 varint of exactly nbytes bytes (continuation bytes past the
-    value's own carry zeros): legal for readLong (RLEv1.cc:154-170), which
-    keeps reading until a byte below 0x80; bits past 64 are dropped."""
-    out = []
-    for i in range(nbytes):
-        b = (u >> (7 * i)) & 0x7F if 7 * i < 64 else 0
-        out.append(b | (0x80 if i + 1 < nbytes else 0))
-    return out
-
-
 @pytest.mark.parametrize("nbytes", [11, 16, 40])
 def test_rlev1_overlong_varints_vs_oracle(ctx, nbytes):
     # literal groups whose varints run past 10 bytes: 128 x 40 bytes is longer
@@ -122,18 +112,10 @@ def test_rlev1_overlong_varints_vs_oracle(ctx, nbytes):
         k = 128 if g % 2 == 0 else int(rng.integers(1, 128))
         data.append(256 - k)
         for _ in range(k):
-            data += bytes(_padded_varint(int(rng.integers(0, 1 << 62)), nbytes if rng.random() < 0.7 else 2))
+            data += padded_varint(int(rng.integers(0, 1 << 62)), nbytes if rng.random() < 0.7 else 2)
         data += bytes([5, 3, 7])  # a run of 8: base 7, delta 3
     data = bytes(data)
-    total = 0
-    probe = oracle.RleDecoderV1(data, False)
-    # count the values by decoding until the stream ends
-    while True:
-        try:
-            probe.next(1)
-            total += 1
-        except Exception:
-            break
+    total = model_decode(data, False)[1]  # the values the stream holds
     want = oracle.RleDecoderV1(data, False).next(total)
     got = orc_amd.rlev1_decode(data, total, False, ctx=ctx)
     np.testing.assert_array_equal(got, want)
@@ -146,14 +128,8 @@ def test_rlev1_truncated_in_a_later_window(ctx, cut):
     rng = np.random.default_rng(cut)
     data, vals = encode(random_groups(rng, 20_000, True, 30), True)
     data = data[:cut]
-    dec = oracle.RleDecoderV1(data, True)
-    ok = 0
-    while True:
-        try:
-            dec.next(1)
-            ok += 1
-        except Exception:
-            break
+    ok = model_decode(data, True)[1]  # the values producible before the cut
+    np.testing.assert_array_equal(oracle.RleDecoderV1(data, True).next(ok), vals[:ok])
     got = orc_amd.rlev1_decode(data, ok, True, ctx=ctx)
     np.testing.assert_array_equal(got, vals[:ok])
     with pytest.raises(orc_amd.ParseError, match="bad read in readByte"):
