@@ -71,6 +71,9 @@ void* orcg_ctx_stream(orcg_ctx* ctx);
  * the launches issued since the last call (first error in value order). */
 int orcg_ctx_synchronize(orcg_ctx* ctx);
 const char* orcg_ctx_last_error(const orcg_ctx* ctx);
+/* Value index (row) of the last device-side error collected on this context:
+ * the first failing value in value order of that launch. */
+uint64_t orcg_ctx_last_error_value(const orcg_ctx* ctx);
 
 /* Kernel selection for RLEv2 decode (tuning / A-B measurement). TILED (the
  * default) stages segment chunks through LDS by LDS-DMA and walks headers in
@@ -390,6 +393,42 @@ int orcg_timestamp_decode_tz_device(orcg_ctx* ctx, int64_t* d_seconds, int64_t* 
 int orcg_timestamp_tz_bench(orcg_ctx* ctx, const int64_t* d_seconds_in, const int64_t* d_nanos_in,
                             int64_t* d_seconds, int64_t* d_nanos, uint64_t n, const orcg_timezone* writer_tz,
                             const orcg_timezone* reader_tz, int mode, uint32_t iters, double* ms_out);
+
+/* ---- schema evolution: numeric and decimal conversions --------------------
+ * One decoded column converted to the kind of a read type, value for value as
+ * the reference's ConvertColumnReader does (c++/src/ConvertColumnReader.cc:
+ * 59-207 numeric -> numeric, :342-415 numeric -> decimal, :491-563 decimal ->
+ * numeric, :566-617 decimal -> decimal; convertDecimal, c++/src/Int128.cc:
+ * 534-624). The source class names how the n values lie in d_src (the batch
+ * layout of orcg_reader.h): */
+enum {
+  ORCG_CONVERT_INT64 = 0,     /* int64: boolean, tinyint, smallint, int, bigint */
+  ORCG_CONVERT_FLOAT = 1,     /* double holding a float value: float */
+  ORCG_CONVERT_DOUBLE = 2,    /* double */
+  ORCG_CONVERT_DECIMAL64 = 3, /* int64, unscaled at src_scale */
+  ORCG_CONVERT_DECIMAL128 = 4 /* [hi, lo] int64 pairs, unscaled at src_scale */
+};
+/* target_kind is the read type's Type.Kind (ORCG_TYPE_BOOLEAN .. ORCG_TYPE_DOUBLE
+ * or ORCG_TYPE_DECIMAL with precision and scale; src_scale counts for decimal
+ * sources only). d_out receives int64 (boolean and the integers: the narrowed
+ * value), double (float: the float-rounded value; double), int64 (decimal,
+ * precision <= 18) or [hi, lo] int64 pairs (precision > 18). d_not_null (NULL =
+ * every row set) is only read; d_out_not_null[n] is always written: 1 for a
+ * set row whose value the target holds, else 0, and such a row's slot holds 0.
+ * *nulled = the set rows the conversion turned into NULLs (handleOverflow,
+ * :66-76). With throw_on_overflow the first of them in value order fails the
+ * call: ORCG_PARSE_ERROR, "Overflow when convert from <source> to <target>"
+ * (the reference's SchemaEvolutionError, which prints typeid names), its row in
+ * no particular slot of the outputs. Synchronous. */
+int orcg_convert_column_device(orcg_ctx* ctx, const void* d_src, int src_class, int32_t src_scale, uint64_t n,
+                               const uint8_t* d_not_null, uint32_t target_kind, uint32_t precision, uint32_t scale,
+                               int throw_on_overflow, void* d_out, uint8_t* d_out_not_null, uint64_t* nulled);
+
+/* Measurement helper (no reference counterpart): `iters` timed launches of
+ * that conversion (overflows nulled), ms_out[i] = HIP-event time of launch i. */
+int orcg_convert_bench(orcg_ctx* ctx, const void* d_src, int src_class, int32_t src_scale, uint64_t n,
+                       const uint8_t* d_not_null, uint32_t target_kind, uint32_t precision, uint32_t scale, void* d_out,
+                       uint8_t* d_out_not_null, uint32_t iters, double* ms_out);
 
 /* IntegerColumnReader<LongVectorBatch>::next for a whole stripe column
  * (c++/src/ColumnReader.cc:81-104, 224-258): PRESENT (boolean RLE; NULL/0 if

@@ -38,6 +38,9 @@
  * decoding (orcg_reader_set_lazy_dictionary, RowReaderOptions::
  * setEnableLazyDecoding) only those are produced (data / length are NULL).
  * Null slots hold 0 (the reference leaves them unspecified).
+ * Under a read type (orcg_reader_set_read_type) a converted column has the
+ * layout of its read kind: integers of every width int64 holding the narrowed
+ * value, FLOAT double holding the float-rounded value.
  *
  * TIMESTAMP columns are adjusted from the stripe's writer zone to the reader
  * zone (default "GMT") as TimestampColumnReader does (ColumnReader.cc:280-349)
@@ -160,6 +163,33 @@ int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on);
  * throw_on_overflow = 1 (the reference's default) is supported. */
 int orcg_reader_set_hive11_decimal(orcg_reader* r, int32_t forced_scale, int throw_on_overflow);
 int32_t orcg_reader_hive11_scale(const orcg_reader* r);
+/* Schema evolution (RowReaderOptions::setReadType, c++/include/orc/Reader.hh;
+ * SchemaEvolution.cc, ConvertColumnReader.cc): read the file under another
+ * type. type_string follows Type::buildTypeFromString's grammar, the inverse
+ * of Type::toString (decimal(p,s), varchar(n), char(n), array<>, map<,>,
+ * struct<n:t,...>, uniontype<>, timestamp with local time zone); NULL or ""
+ * clears it. The read type must have the file type's shape (the same column
+ * ids and child counts; field names are not compared). Built: numeric ->
+ * numeric, numeric -> decimal, decimal -> numeric, decimal -> decimal
+ * (orcg_convert_column_device's rules); same kinds pass through untouched.
+ * ORCG_INVALID_ARGUMENT with "Conversion from <file type> to <read type> is
+ * not supported" for what the reference converts and this reader does not
+ * (anything to or from string / char / varchar, a length change included;
+ * anything to timestamp; a precision-0 decimal as a source), and with the
+ * reference's "Cannot convert from <file type> to <read type>" for what it
+ * refuses too (a date, binary or timestamp source; a kind change on a compound
+ * type; another shape). A converted column's view reports the read kind and
+ * has its layout; orcg_reader_type keeps reporting the file's type. */
+int orcg_reader_set_read_type(orcg_reader* r, const char* type_string);
+/* RowReaderOptions::throwOnSchemaEvolutionOverflow (default off: a value the
+ * read type cannot hold reads as NULL). On: the first such row in value order
+ * of the first such column in column order fails the read, ORCG_PARSE_ERROR,
+ * "Overflow when convert from <file type> to <read type>" (the reference
+ * prints typeid names); within a column a decode error comes first. */
+int orcg_reader_set_throw_on_schema_evolution_overflow(orcg_reader* r, int on);
+/* The type column type_id is read as: the read type's node where it converts,
+ * else the file's (SchemaEvolution::getReadType). */
+int orcg_reader_read_type(const orcg_reader* r, uint32_t type_id, orcg_type_info* out);
 /* Register the rules of zone `name` (TZif bytes, as orcg_timezone_parse) on
  * this reader: looked up before the UTC names and the zone directory, under
  * the name's alias target (US/Pacific = America/Los_Angeles, Timezone.cc:47-59).
@@ -206,8 +236,8 @@ int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t it
  * instead of 24, and the caller looks each row up in the dictionary
  * (StringDictionaryColumnReader::next, ColumnReader.cc:561-594). A row
  * reader keeps its own
- * RowReaderOptions (include, lazy decoding, time zone: a copy of the reader's
- * zones taken at creation) and device memory; it borrows
+ * RowReaderOptions (include, lazy decoding, time zone, read type and overflow
+ * rule: copies of the reader's taken at creation) and device memory; it borrows
  * the reader (destroy row readers first), whose decodes it takes turns with. */
 typedef struct orcg_row_reader orcg_row_reader;
 typedef struct {

@@ -15,6 +15,7 @@ from .rle import (  # noqa: F401
     RleVersion_1,
     RleVersion_2,
     byterle_decode_device,
+    convert_column_device,
     create_boolean_rle_decoder,
     create_byte_rle_decoder,
     create_java_rle_decoder,

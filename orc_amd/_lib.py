@@ -52,6 +52,7 @@ SIGNATURES = [
     ("orcg_ctx_stream", [vp], vp),
     ("orcg_ctx_synchronize", [vp], i32),
     ("orcg_ctx_last_error", [vp], cp),
+    ("orcg_ctx_last_error_value", [vp], u64),
     ("orcg_ctx_set_rlev2_variant", [vp, i32], i32),
     ("orcg_rlev2_variants", [vp, i32], i32),
     ("orcg_version", [], cp),
@@ -98,6 +99,10 @@ SIGNATURES = [
     ("orcg_decimal_decode_device", [vp, vp, u64, vp, u64, ctypes.c_uint32, i32, vp], i32),
     ("orcg_hive11_decimal_decode_device", [vp, vp, u64, vp, u64, i32, i32, vp, vp], i32),
     ("orcg_timestamp_decode_device", [vp, vp, vp, u64, ctypes.c_int64], i32),
+    ("orcg_convert_column_device", [vp, vp, i32, i32, u64, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, i32,
+                                    vp, vp, ctypes.POINTER(u64)], i32),
+    ("orcg_convert_bench", [vp, vp, i32, i32, u64, vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, vp, vp,
+                            ctypes.c_uint32, ctypes.POINTER(ctypes.c_double)], i32),
     ("orcg_timezone_parse", [cp, cp, u64, ctypes.POINTER(vp)], i32),
     ("orcg_timezone_load", [cp, ctypes.POINTER(vp)], i32),
     ("orcg_timezone_destroy", [vp], None),
@@ -190,6 +195,9 @@ SIGNATURES += [
     ("orcg_reader_set_lazy_dictionary", [vp, i32], i32),
     ("orcg_reader_set_hive11_decimal", [vp, i32, i32], i32),
     ("orcg_reader_hive11_scale", [vp], i32),
+    ("orcg_reader_set_read_type", [vp, cp], i32),
+    ("orcg_reader_set_throw_on_schema_evolution_overflow", [vp, i32], i32),
+    ("orcg_reader_read_type", [vp, u32, ctypes.POINTER(TypeInfo)], i32),
     ("orcg_reader_set_zone_rules", [vp, cp, cp, u64], i32),
     ("orcg_reader_set_timezone_name", [vp, cp], i32),
     ("orcg_reader_set_local_timezone", [vp, cp], i32),

@@ -542,6 +542,21 @@ class RowReaderOptions {
     timezone_ = zoneName;
     return *this;
   }
+  // Schema evolution (c++/include/orc/Reader.hh setReadType, here as a type
+  // string in Type::buildTypeFromString's grammar; "" = the file's type) and
+  // throwOnSchemaEvolutionOverflow (default false: a value the read type
+  // cannot hold reads as NULL). Needs setUseTightNumericVector(true), as in
+  // the reference.
+  RowReaderOptions& setReadType(const std::string& typeString) {
+    readType_ = typeString;
+    return *this;
+  }
+  RowReaderOptions& throwOnSchemaEvolutionOverflow(bool on) {
+    evoThrow_ = on;
+    return *this;
+  }
+  const std::string& getReadType() const { return readType_; }
+  bool getThrowOnSchemaEvolutionOverflow() const { return evoThrow_; }
   const std::string& getTimezoneName() const { return timezone_; }
   bool getUseTightNumericVector() const { return tight_; }
   uint64_t getOffset() const { return offset_; }
@@ -557,6 +572,8 @@ class RowReaderOptions {
   bool lazy_ = false;
   bool tight_ = false;
   std::string timezone_ = "GMT";
+  std::string readType_;
+  bool evoThrow_ = false;
 };
 
 // orc::ReaderOptions (c++/include/orc/Reader.hh:112-200): the memory pool
@@ -628,6 +645,8 @@ class RowReader {
   std::vector<std::vector<uint32_t>> subs_;
   std::vector<uint8_t> subs_known_;
   std::vector<orcg_type_info> types_;
+  // under a read type: per type id the type it is read as (taken at creation)
+  std::vector<orcg_type_info> read_types_;
   const std::vector<uint32_t>& subs(uint32_t id, uint32_t kind);
   void new_stripe();
   // the batch's bulk copies (slab -> batch buffers), run together at the end
@@ -725,9 +744,11 @@ class Reader {
 
 using Selected = std::function<bool(uint32_t)>;
 
+// read_types (may be null): per type id the type the column is read as
 inline std::unique_ptr<ColumnVectorBatch> make_batch(const Reader& r, uint32_t id, uint64_t cap, bool lazy,
-                                                     const Selected& sel, bool tight = false) {
-  const orcg_type_info t = r.getType(id);
+                                                     const Selected& sel, bool tight = false,
+                                                     const std::vector<orcg_type_info>* read_types = nullptr) {
+  const orcg_type_info t = read_types && id < read_types->size() ? (*read_types)[id] : r.getType(id);
   MemoryPool& pool = r.getMemoryPool();
   switch (t.kind) {
     case ORCG_TYPE_BOOLEAN:
@@ -758,26 +779,26 @@ inline std::unique_ptr<ColumnVectorBatch> make_batch(const Reader& r, uint32_t i
     case ORCG_TYPE_TIMESTAMP_INSTANT: return std::make_unique<TimestampVectorBatch>(t.kind, cap, pool);
     case ORCG_TYPE_LIST: {
       auto b = std::make_unique<ListVectorBatch>(t.kind, cap, pool);
-      b->elements = make_batch(r, r.getSubtypes(id)[0], cap, lazy, sel, tight);
+      b->elements = make_batch(r, r.getSubtypes(id)[0], cap, lazy, sel, tight, read_types);
       return b;
     }
     case ORCG_TYPE_MAP: {
       auto b = std::make_unique<MapVectorBatch>(t.kind, cap, pool);
       const auto s = r.getSubtypes(id);
-      b->keys = make_batch(r, s[0], cap, lazy, sel, tight);
-      b->elements = make_batch(r, s[1], cap, lazy, sel, tight);
+      b->keys = make_batch(r, s[0], cap, lazy, sel, tight, read_types);
+      b->elements = make_batch(r, s[1], cap, lazy, sel, tight, read_types);
       return b;
     }
     case ORCG_TYPE_STRUCT: {
       // the selected fields only (Type::createRowBatch of the selected type)
       auto b = std::make_unique<StructVectorBatch>(t.kind, cap, pool);
       for (uint32_t s : r.getSubtypes(id))
-        if (sel(s)) b->fields.push_back(make_batch(r, s, cap, lazy, sel, tight));
+        if (sel(s)) b->fields.push_back(make_batch(r, s, cap, lazy, sel, tight, read_types));
       return b;
     }
     case ORCG_TYPE_UNION: {
       auto b = std::make_unique<UnionVectorBatch>(t.kind, cap, pool);
-      for (uint32_t s : r.getSubtypes(id)) b->children.push_back(make_batch(r, s, cap, lazy, sel, tight));
+      for (uint32_t s : r.getSubtypes(id)) b->children.push_back(make_batch(r, s, cap, lazy, sel, tight, read_types));
       return b;
     }
     default: return std::make_unique<LongVectorBatch>(t.kind, cap, pool);
@@ -802,7 +823,26 @@ inline RowReader::RowReader(Reader& r, const RowReaderOptions& opts)
     o.include = inc.data();
     o.include_len = nt;
   }
-  r_.check(orcg_row_reader_create(r.get(), &o, &rr_));
+  if (!opts.getReadType().empty()) {
+    // ConvertColumnReader.cc:1274
+    if (!tight_)
+      throw InvalidArgument(
+          "SchemaEvolution only support tight vector, please create ColumnVectorBatch with option "
+          "useTightNumericVector");
+    // the row reader copies the reader's read type and overflow rule at its
+    // creation: they are set for the creation alone (not from two threads at once)
+    r_.check(orcg_reader_set_read_type(r.get(), opts.getReadType().c_str()));
+    (void)orcg_reader_set_throw_on_schema_evolution_overflow(r.get(), opts.getThrowOnSchemaEvolutionOverflow() ? 1 : 0);
+    const uint32_t nt = orcg_reader_num_types(r.get());
+    read_types_.resize(nt);
+    for (uint32_t id = 0; id < nt; ++id) (void)orcg_reader_read_type(r.get(), id, &read_types_[id]);
+    const int rc = orcg_row_reader_create(r.get(), &o, &rr_);
+    (void)orcg_reader_set_read_type(r.get(), nullptr);
+    (void)orcg_reader_set_throw_on_schema_evolution_overflow(r.get(), 0);
+    r_.check(rc);
+  } else {
+    r_.check(orcg_row_reader_create(r.get(), &o, &rr_));
+  }
   // helper threads for the batch copies: ORCG_COPY_THREADS, else up to 3
   // beside the caller's (a quarter of the host's threads)
   unsigned helpers = 0;
@@ -816,7 +856,8 @@ inline RowReader::RowReader(Reader& r, const RowReaderOptions& opts)
 }
 
 inline std::unique_ptr<ColumnVectorBatch> RowReader::createRowBatch(uint64_t capacity) const {
-  return make_batch(r_, 0, capacity, lazy_, [this](uint32_t id) { return isSelected(id); }, tight_);
+  return make_batch(r_, 0, capacity, lazy_, [this](uint32_t id) { return isSelected(id); }, tight_,
+                    read_types_.empty() ? nullptr : &read_types_);
 }
 
 inline bool RowReader::next(ColumnVectorBatch& batch) {
@@ -865,7 +906,7 @@ inline const std::vector<uint32_t>& RowReader::subs(uint32_t id, uint32_t kind) 
   if (!subs_known_[id]) {
     for (uint32_t s : r_.getSubtypes(id))
       if (kind != ORCG_TYPE_STRUCT || isSelected(s)) subs_[id].push_back(s);
-    types_[id] = r_.getType(id);
+    types_[id] = id < read_types_.size() ? read_types_[id] : r_.getType(id);
     subs_known_[id] = 1;
   }
   return subs_[id];

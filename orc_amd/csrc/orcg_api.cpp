@@ -38,6 +38,7 @@ const char* dev_error_message(uint32_t code) {
       return "Corruption in ORC data encountered. To skip reading corrupted data, set "
              "hive.exec.orc.skip.corrupt.data to true";
     case kErrJavaPatchIndex: return "Index 0 out of bounds for length 0";
+    case kErrConvertOverflow: return "Overflow when convert";
   }
   return "unknown device error";
 }
@@ -466,6 +467,8 @@ int orcg_ctx_set_rlev2_variant(orcg_ctx* c, int v) {
 void* orcg_ctx_stream(orcg_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 const char* orcg_ctx_last_error(const orcg_ctx* c) { return c ? c->last_error.c_str() : ""; }
+
+uint64_t orcg_ctx_last_error_value(const orcg_ctx* c) { return c ? c->last_error_value : 0; }
 
 int orcg_ctx_synchronize(orcg_ctx* c) { return c ? sync_ctx(c) : ORCG_INVALID_ARGUMENT; }
 

@@ -29,6 +29,8 @@ enum DevErr : uint32_t {
   // Java face (RunLengthIntegerReaderV2.java, readPatchedBaseValues :149-260)
   kErrJavaCorrupt = 11,    // IOException "Corruption in ORC data encountered. ..." (pw + pgw > 64, :196-200)
   kErrJavaPatchIndex = 12, // ArrayIndexOutOfBoundsException: pl == 0 reads unpackedPatch[0] (:207)
+  // schema evolution (ConvertColumnReader.cc handleOverflow, :66-76); the caller appends the type names
+  kErrConvertOverflow = 13, // "Overflow when convert from <file type> to <read type>"
 };
 
 const char* dev_error_message(uint32_t code);
@@ -347,6 +349,36 @@ struct TzTable {
 // writer zone's epoch is in its table)
 int launch_timestamp_tz(Ctx* ctx, int64_t* d_secs, int64_t* d_nanos, uint64_t n, const TzTable& writer,
                         const TzTable& reader);
+
+// Schema evolution (convert_kernels.hip): n decoded values of class `src`
+// (ConvSrc) converted to class `dst` (ConvDst) by the reference's rules
+// (ConvertColumnReader.cc). nn (may be null = every row set) is read only;
+// out_nn[i] = the row is set and its value fits; a row that does not fit holds
+// 0 and adds one to *nulled (device; the caller zeroes it). throw_mode: the
+// first such row is also reported into err as kErrConvertOverflow.
+enum ConvSrc { kConvInt64 = 0, kConvFloat = 1, kConvDouble = 2, kConvDec64 = 3, kConvDec128 = 4 };
+enum ConvDst { kToBool = 0, kToInt = 1, kToFloat = 2, kToDouble = 3, kToDec64 = 4, kToDec128 = 5 };
+struct ConvertArgs {
+  const void* src;
+  const uint8_t* nn;
+  void* out;
+  uint8_t* out_nn;
+  uint64_t n;
+  unsigned long long* err;
+  unsigned long long* nulled;
+  int32_t src_scale;         // decimal sources
+  int32_t width;             // kToInt: bytes of the read type (1, 2, 4, 8)
+  int32_t precision, scale;  // decimal targets
+  int32_t throw_mode;
+  // host-computed constants (convert_constants): 10^src_scale as the double and
+  // the float the reference divides by, and (T)pow(10, scale) for a float or
+  // double source (a float's held in a double)
+  float factor_f;
+  double factor_d;
+  double pow_t;
+};
+void convert_constants(int src, ConvertArgs* a);
+int launch_convert(Ctx* ctx, int src, int dst, const ConvertArgs& a);
 
 // Row-index segmentation (column_kernels.hip): prefix[g] = non-zero bytes of
 // mask before row rows[g] (counts: scratch of G entries; prefix: G + 1);

@@ -167,6 +167,60 @@ int orcg_reader_set_hive11_decimal(orcg_reader* r, int32_t forced_scale, int thr
 }
 int32_t orcg_reader_hive11_scale(const orcg_reader* r) { return r ? r->hive11_scale : 6; }
 
+int orcg_reader_set_read_type(orcg_reader* r, const char* type_string) {
+  if (!r) return ORCG_INVALID_ARGUMENT;
+  std::shared_ptr<ReadPlan> plan;
+  if (type_string && *type_string) {
+    plan.reset(new ReadPlan());
+    plan->text = type_string;
+    std::string err;
+    if (!rt::parse_type(plan->text, &plan->tree, &err)) return r->fail_user(ORCG_INVALID_ARGUMENT, err);
+    if (!rt::plan_conversion(r->file_tree(), plan->tree, &plan->conv, &err))
+      return r->fail_user(ORCG_INVALID_ARGUMENT, err);
+  }
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->own_read = plan;
+  return ORCG_OK;
+}
+
+int orcg_reader_set_throw_on_schema_evolution_overflow(orcg_reader* r, int on) {
+  if (!r) return ORCG_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->own_evo_throw = on != 0;
+  return ORCG_OK;
+}
+
+int orcg_reader_read_type(const orcg_reader* r, uint32_t id, orcg_type_info* out) {
+  if (!r || !out || id >= r->footer.types.size()) return ORCG_INVALID_ARGUMENT;
+  const std::shared_ptr<const ReadPlan> plan = r->own_read;
+  if (!plan || plan->conv[id] != rt::kConvert) return orcg_reader_type(r, id, out);
+  const rt::Node& n = plan->tree[id];
+  out->kind = n.kind;
+  out->num_subtypes = (uint32_t)n.subtypes.size();
+  out->maximum_length = n.maximum_length;
+  out->precision = n.precision;
+  out->scale = n.scale;
+  return ORCG_OK;
+}
+
+}  // extern "C"
+
+rt::Tree orcg_reader::file_tree() const {
+  rt::Tree t(footer.types.size());
+  for (size_t i = 0; i < t.size(); ++i) {
+    const TypeInfo& f = footer.types[i];
+    t[i].kind = f.kind;
+    t[i].maximum_length = f.maximum_length;
+    t[i].precision = f.precision;
+    t[i].scale = f.scale;
+    t[i].subtypes = f.subtypes;
+    t[i].field_names = f.field_names;
+  }
+  return t;
+}
+
+extern "C" {
+
 int orcg_reader_set_zone_rules(orcg_reader* r, const char* name, const uint8_t* tzif, uint64_t len) {
   if (!r || !name || !*name || (len && !tzif)) return ORCG_INVALID_ARGUMENT;
   std::unique_ptr<ZoneEntry> e(new ZoneEntry());
@@ -257,14 +311,16 @@ int orcg_reader_read_stripe(orcg_reader* r, uint64_t stripe) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
+                          r->own_evo_throw);
   return r->read_stripes(stripe, 1);
 }
 
 int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t iters, double* decode_s, double* h2d_s) {
   if (!r || !decode_s || !h2d_s || iters == 0) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
+                          r->own_evo_throw);
   if (!r->ctx) return r->fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (stripe >= r->footer.stripes.size()) return r->fail(ORCG_INVALID_ARGUMENT, "stripe index out of range");
   hipSetDevice(r->ctx->device);
@@ -286,7 +342,8 @@ int orcg_reader_read_stripes(orcg_reader* r, uint64_t first, uint64_t count) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz);
+  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
+                          r->own_evo_throw);
   return r->read_stripes(first, count);
 }
 
@@ -295,7 +352,7 @@ int orcg_reader_stripe_column(const orcg_reader* r, uint64_t k, uint32_t id, orc
   const ColOut& c = r->slots[k]->out[id];
   memset(out, 0, sizeof(*out));
   out->type_id = id;
-  out->kind = r->footer.types[id].kind;
+  out->kind = c.converted ? c.rkind : r->footer.types[id].kind;
   fill_view(c, out);
   return ORCG_OK;
 }

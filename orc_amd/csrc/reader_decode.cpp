@@ -33,11 +33,16 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
   if (rc) return rc;
   const StreamLayout lay = layout(id, c);
   const uint32_t k = c.kind;
-  if (k == ORCG_TYPE_DECIMAL) return decode_decimal(id, c, lay, r);
+  c.converted = false;
+  // schema evolution: a numeric or decimal column whose read type differs is
+  // converted once its kind's decode has placed its rows
+  const bool convert = read && id < read->conv.size() && read->conv[id] == rt::kConvert;
+  auto then_convert = [&](int rc) { return rc || !convert ? rc : convert_column(id, c); };
+  if (k == ORCG_TYPE_DECIMAL) return then_convert(decode_decimal(id, c, lay, r));
   if (is_timestamp_kind(k)) return decode_timestamp(c, lay, r);
-  if (is_int_kind(k)) return decode_integer(c, lay, r);
-  if (k == ORCG_TYPE_BOOLEAN || k == ORCG_TYPE_BYTE) return decode_bytes(c, lay, r);
-  if (k == ORCG_TYPE_FLOAT || k == ORCG_TYPE_DOUBLE) return decode_double(c, r);
+  if (is_int_kind(k)) return then_convert(decode_integer(c, lay, r));
+  if (k == ORCG_TYPE_BOOLEAN || k == ORCG_TYPE_BYTE) return then_convert(decode_bytes(c, lay, r));
+  if (k == ORCG_TYPE_FLOAT || k == ORCG_TYPE_DOUBLE) return then_convert(decode_double(c, r));
   if (is_string_kind(k)) return is_dict(c.encoding) ? decode_dict_string(id, c, lay, r) : decode_direct_string(id, c, lay, r);
   if (k == ORCG_TYPE_LIST || k == ORCG_TYPE_MAP) return decode_list(id, c, lay, r);
   if (k == ORCG_TYPE_STRUCT) return decode_struct(id, c, r);
@@ -206,6 +211,85 @@ int orcg_reader::decode_hive11_nulls(Col& c, const uint8_t* keep, const Rows& r)
     if (*kept < n) {
       cp->has_nulls = true;
       cp->nn = rnn;
+    }
+    return ORCG_OK;
+  });
+  return ORCG_OK;
+}
+
+// ConvertColumnReader::next (ConvertColumnReader.cc:38-48, and the readers
+// built on it): the file type's column is read first (c.data, c.nn), then each
+// set row is converted to the read type. One launch a converted column; the
+// rows it nulled are counted into a read-back slot, and a check after the
+// column's own PRESENT check settles has_nulls and the mask. The incoming mask
+// may be the parent's buffer: the kernel writes a new one.
+int orcg_reader::convert_column(uint32_t id, Col& c) {
+  const TypeInfo& ft = footer.types[id];
+  const rt::Node& rn = read->tree[id];
+  c.converted = true;
+  c.rkind = rn.kind;
+  c.rprecision = rn.precision;
+  c.rscale = rn.scale;
+  const uint64_t n = c.n;
+  if (n == 0) return ORCG_OK;
+  int src;
+  if (ft.kind == ORCG_TYPE_DECIMAL) src = ft.precision <= 18 ? kConvDec64 : kConvDec128;
+  else if (ft.kind == ORCG_TYPE_FLOAT) src = kConvFloat;
+  else if (ft.kind == ORCG_TYPE_DOUBLE) src = kConvDouble;
+  else src = kConvInt64;
+  ConvertArgs a{};
+  int dst;
+  switch (rn.kind) {
+    case ORCG_TYPE_BOOLEAN: dst = kToBool; break;
+    case ORCG_TYPE_BYTE: dst = kToInt, a.width = 1; break;
+    case ORCG_TYPE_SHORT: dst = kToInt, a.width = 2; break;
+    case ORCG_TYPE_INT: dst = kToInt, a.width = 4; break;
+    case ORCG_TYPE_LONG: dst = kToInt, a.width = 8; break;
+    case ORCG_TYPE_FLOAT: dst = kToFloat; break;
+    case ORCG_TYPE_DOUBLE: dst = kToDouble; break;
+    default: dst = rn.precision <= 18 ? kToDec64 : kToDec128; break;
+  }
+  int rc;
+  ORCG_ALLOC(int64_t, out, dst == kToDec128 ? 2 * n : n);
+  ORCG_ALLOC(uint8_t, out_nn, n + 8);
+  // [0] the rows nulled, [1] the first overflowing row (throw mode): a record
+  // of its own, so that a decode error of this column, whatever its row, wins
+  const uint64_t* h = nullptr;
+  uint64_t* slots = rb_alloc(2, &h);
+  if (!slots) {
+    ORCG_ALLOC_TO(uint64_t, slots, 2);
+    if ((rc = hip_check(ctx, hipMemsetAsync(slots, 0, 8, ctx->stream), "memset"))) return fail_ctx(rc);
+  }
+  if (evo_throw && (rc = hip_check(ctx, hipMemsetAsync(slots + 1, 0xff, 8, ctx->stream), "memset"))) return fail_ctx(rc);
+  a.src = c.data;
+  a.nn = c.has_nulls ? c.nn : nullptr;
+  a.out = out;
+  a.out_nn = out_nn;
+  a.n = n;
+  a.err = (unsigned long long*)(slots + 1);
+  a.nulled = (unsigned long long*)slots;
+  a.src_scale = (int32_t)ft.scale;
+  a.precision = (int32_t)rn.precision;
+  a.scale = (int32_t)rn.scale;
+  a.throw_mode = evo_throw ? 1 : 0;
+  convert_constants(src, &a);
+  if ((rc = launch_convert(ctx, src, dst, a))) return fail_ctx(rc);
+  if (!h && !(h = defer(slots, 2))) return fail(ORCG_DEVICE_ERROR, "D2H of the conversion's counts failed");
+  c.data = out;
+  if (c.has_nulls) c.nn = out_nn;  // the incoming nulls and the overflows
+  Col* cp = &c;
+  const uint64_t* rec = F->h_rb + cur_col;  // the column's own error record, read back with the stripe
+  const bool thrown = evo_throw;
+  const std::shared_ptr<const ReadPlan> plan = read;
+  F->checks.emplace_back(cur_col, [this, cp, h, out_nn, rec, thrown, id, plan]() -> int {
+    if (thrown && h[1] != kNoError && *rec == kNoError) {
+      if (ctx) ctx->last_error_value = h[1] >> 8;
+      return fail(ORCG_PARSE_ERROR, std::string(dev_error_message(kErrConvertOverflow)) + " from " +
+                                        rt::to_string(file_tree(), id) + " to " + rt::to_string(plan->tree, id));
+    }
+    if (h[0]) {
+      cp->has_nulls = true;
+      cp->nn = out_nn;
     }
     return ORCG_OK;
   });

@@ -34,6 +34,7 @@
 #include "../../include/orcg_reader.h"
 #include "orc_file.hh"
 #include "orcg_internal.hh"
+#include "read_type.hh"
 #include "reader_layout.hh"
 #include "timezone.hh"
 
@@ -199,6 +200,21 @@ struct ColView {
   const int64_t* index = nullptr;         // dictionary strings: entry of each row (EncodedStringVectorBatch::index)
   const int64_t* dict_offsets = nullptr;  // dictionary strings: dict_size + 1 entry offsets (StringDictionary)
   uint64_t dict_size = 0;                 // ColumnEncoding.dictionarySize of this stripe
+  // schema evolution: the column was converted to the read type's kind
+  // (orcg_reader::convert_column); `kind` stays the file's
+  bool converted = false;
+  uint32_t rkind = 0, rprecision = 0, rscale = 0;
+  // the kind, and for a decimal the precision, the batch layout follows
+  uint32_t out_kind() const { return converted ? rkind : kind; }
+  uint32_t out_precision(uint32_t file_precision) const { return converted ? rprecision : file_precision; }
+};
+
+// A read type set on a reader (RowReaderOptions::setReadType): its tree, the
+// conversion of each node against the file type (read_type.hh), its text
+struct ReadPlan {
+  rt::Tree tree;
+  std::vector<rt::Conv> conv;
+  std::string text;
 };
 
 // A column of a stripe being prepared and decoded: its streams, and the view
@@ -352,11 +368,19 @@ struct orcg_reader {
   const ZoneEntry* utc_zone_entry() const;                       // caller holds tz_mu
   const ZoneEntry* resolve_zone(const std::string& name) const;  // NULL: not found
   int zone_table(const ZoneEntry* z, TzTable* out);
+  // Schema evolution (RowReaderOptions::setReadType /
+  // throwOnSchemaEvolutionOverflow): the reader's own, and those of the decode
+  // in progress. A plan is immutable once set; row readers share it.
+  std::shared_ptr<const ReadPlan> own_read, read;
+  bool own_evo_throw = false, evo_throw = false;
+  rt::Tree file_tree() const;  // the file's types as read_type.hh's tree
   struct Active {
     orcg_reader* r;
     Active(orcg_reader* r_, Ctx* c, const std::vector<uint8_t>& sel, bool lazy, const ZoneEntry* rtz,
-           const std::string& ltz)
+           const std::string& ltz, std::shared_ptr<const ReadPlan> rd, bool evo)
         : r(r_) {
+      r->read = std::move(rd);
+      r->evo_throw = evo;
       r->ctx = c;
       r->selected = sel;
       r->lazy_dict = lazy;
@@ -588,6 +612,9 @@ struct orcg_reader {
   // one per column kind (reader_decode.cpp; the struct's fork: reader_fork.cpp)
   int decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, const Rows& r);
   int decode_hive11_nulls(Col& c, const uint8_t* keep, const Rows& r);
+  // schema evolution: the decoded column `id` converted to its read type
+  // (convert_kernels.hip), right after its kind's decode placed its rows
+  int convert_column(uint32_t id, Col& c);
   int decode_timestamp(Col& c, const StreamLayout& lay, const Rows& r);
   int decode_integer(Col& c, const StreamLayout& lay, const Rows& r);
   int decode_bytes(Col& c, const StreamLayout& lay, const Rows& r);

@@ -34,9 +34,11 @@ static void col_buffers(const ColOut& o, const TypeInfo& t, std::vector<std::pai
     if (p && bytes) b.push_back({f, bytes});
   };
   if (o.has_nulls) add(kFNn, o.nn, n);
-  const uint32_t k = o.kind;
+  // a converted column has the layout of its read kind
+  const uint32_t k = o.out_kind();
   if (k == ORCG_TYPE_DECIMAL) {
-    add(kFData, o.data, (t.precision > 18 || t.precision == 0 ? 16 : 8) * n);
+    const uint32_t p = o.out_precision(t.precision);
+    add(kFData, o.data, (p > 18 || p == 0 ? 16 : 8) * n);
   } else if (k == ORCG_TYPE_LIST || k == ORCG_TYPE_MAP) {
     add(kFOffsets, o.offsets, 8 * (n + 1));
   } else if (k == ORCG_TYPE_UNION) {
@@ -85,6 +87,8 @@ struct orcg_row_reader {
   bool lazy_dict = false;
   const ZoneEntry* reader_tz = nullptr;  // setTimezoneName (nullptr: GMT)
   std::string local_tz;                  // the zone of stripes that name none
+  std::shared_ptr<const ReadPlan> read;  // setReadType: the reader's at creation
+  bool evo_throw = false;                // throwOnSchemaEvolutionOverflow, likewise
   uint64_t nstripes = 0, first = 0, last = 0;  // stripes [first, last) are in range
   uint64_t current = 0, row_in_stripe = 0, rows_in_stripe = 0;
   uint64_t previous_row = 0;
@@ -251,7 +255,7 @@ struct orcg_row_reader {
     if (prepared[t & 1] == t) start_ahead();
     {
       std::lock_guard<std::mutex> lk(r->mu);
-      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz);
+      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz, read, evo_throw);
       (void)hipSetDevice(r->ctx->device);
       rc = ORCG_OK;
       if (prepared[t & 1] != t) {
@@ -389,6 +393,9 @@ int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* o, orc
     std::lock_guard<std::mutex> lk(r->mu);
     rr->reader_tz = r->own_reader_tz;
     rr->local_tz = r->own_local_tz;
+    // and of its read type and overflow rule
+    rr->read = r->own_read;
+    rr->evo_throw = r->own_evo_throw;
   }
   if (o && o->timezone) {
     const ZoneEntry* z = r->resolve_zone(o->timezone);
@@ -530,6 +537,7 @@ int orcg_row_reader_column(const orcg_row_reader* rr, uint32_t id, orcg_column_v
   if (!rr->in_batch[id] || !rr->cur) return ORCG_OK;  // no batch, or the column is not decoded
   const ColOut& c = rr->cur->out[id];
   fill_view(c, view);
+  if (c.converted) view->kind = c.rkind;
   if (!c.decoded) return ORCG_OK;
   *begin = rr->begin[id];
   *count = rr->count[id];

@@ -38,6 +38,9 @@ _EPOCH = datetime.date(1970, 1, 1)
 _DECIMAL_CTX = decimal.Context(prec=40)
 
 
+_KEEP = object()  # create_row_reader: keep the reader's read type / overflow rule
+
+
 class UnionValue(tuple):
     """One UNION row: (tag, value) — UnionVectorBatch tags / offsets resolved."""
 
@@ -94,16 +97,19 @@ class ColumnBatch:
 class Batch:
     """One stripe of decoded columns, keyed by type id."""
 
-    def __init__(self, reader, columns):
+    def __init__(self, reader, columns, types=None):
         self.reader = reader
         self.columns = columns
+        # the types the columns were read as: the file's, or under a read
+        # type (Reader.set_read_type) the read type's where a column converts
+        self.types = reader.types if types is None else types
 
     @property
     def num_rows(self):
         return self.columns[0].num_elements
 
     def value(self, tid, i):
-        t = self.reader.types[tid]
+        t = self.types[tid]
         c = self.columns.get(tid)
         if c is None:
             raise KeyError("column %d (%s) was not decoded" % (tid, KIND_NAMES[t.kind]))
@@ -154,7 +160,7 @@ class Batch:
     def to_pylist(self, fields=None):
         """Rows of the root struct as dicts (pyarrow Table.to_pylist shape);
         a non-struct root gives its values."""
-        root = self.reader.types[0]
+        root = self.types[0]
         if root.kind != STRUCT:
             return [self.value(0, i) for i in range(self.num_rows)]
         names = [n for n in root.field_names if fields is None or n in fields]
@@ -182,10 +188,13 @@ class Reader:
             check(rc, lambda: msg)
         self._h = h
         self.types = [self._type(i) for i in range(self._L.orcg_reader_num_types(h))]
+        self._read_type = None      # the read type string (set_read_type)
+        self._read_types = None     # per type id, the type it is read as
+        self._throw_on_overflow = False
 
-    def _type(self, i):
+    def _type(self, i, read=False):
         ti = _lib.TypeInfo()
-        check(self._L.orcg_reader_type(self._h, i, ctypes.byref(ti)))
+        check((self._L.orcg_reader_read_type if read else self._L.orcg_reader_type)(self._h, i, ctypes.byref(ti)))
         subs = (ctypes.c_uint32 * max(ti.num_subtypes, 1))()
         check(self._L.orcg_reader_subtypes(self._h, i, subs, ti.num_subtypes))
         names = []
@@ -261,6 +270,37 @@ class Reader:
         if k in (VARCHAR, CHAR):
             return "%s(%d)" % (KIND_NAMES[k], t.maximum_length)
         return KIND_NAMES[k]
+
+    def set_read_type(self, type_string=None, throw_on_overflow=None):
+        """RowReaderOptions::setReadType: read the file under another type
+        (a type string as type_string() prints it; None clears it). Numeric
+        and decimal columns convert on the GPU by the reference's
+        ConvertColumnReader rules; a value the read type cannot hold reads as
+        NULL, or with throw_on_overflow (throwOnSchemaEvolutionOverflow)
+        raises "Overflow when convert from ... to ...". InvalidArgument for
+        a conversion the reference refuses ("Cannot convert from ...") or
+        this reader does not build ("Conversion from ... is not supported")."""
+        check(self._L.orcg_reader_set_read_type(self._h, None if not type_string else type_string.encode()), self._err)
+        self._read_type = type_string or None
+        self._read_types = [self._type(i, read=True) for i in range(len(self.types))] if type_string else None
+        if throw_on_overflow is not None:
+            check(self._L.orcg_reader_set_throw_on_schema_evolution_overflow(self._h, int(bool(throw_on_overflow))),
+                  self._err)
+            self._throw_on_overflow = bool(throw_on_overflow)
+
+    @property
+    def read_types(self):
+        """Per type id, the type the column is read as (SchemaEvolution::getReadType)."""
+        return self.types if self._read_types is None else self._read_types
+
+    def read_type_string(self, tid=0):
+        """The type the file is read as, as type_string() prints the file's
+        (field names are the file's)."""
+        saved, self.types = self.types, self.read_types
+        try:
+            return self.type_string(tid)
+        finally:
+            self.types = saved
 
     def select(self, type_ids=None):
         """RowReaderOptions::include by type id (None = every column)."""
@@ -384,12 +424,13 @@ class Reader:
         """Decode stripe i on the GPU and copy the selected columns to host."""
         self.read_stripe_device(i)
         cols = {}
-        for t in self.types:
+        types = self.read_types
+        for t in types:
             v = _lib.ColumnView()
             if self._L.orcg_reader_column(self._h, t.id, ctypes.byref(v)) != 0 or not v.decoded:
                 continue
             cols[t.id] = self._column(v, t)
-        return Batch(self, cols)
+        return Batch(self, cols, types)
 
     @property
     def content_length(self):
@@ -445,13 +486,16 @@ class Reader:
         check(self._L.orcg_reader_set_lazy_dictionary(self._h, int(bool(on))), self._err)
 
     def create_row_reader(self, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False,
-                          timezone=None):
+                          timezone=None, read_type=_KEEP, throw_on_overflow=_KEEP):
         """Reader::createRowReader(RowReaderOptions): `include` type ids (or
         top-level field names), range(offset, length) in file bytes,
         setEnableLazyDecoding, setUseTightNumericVector, setTimezoneName
-        (None: the reader's zone, set_timezone)."""
+        (None: the reader's zone, set_timezone), setReadType /
+        throwOnSchemaEvolutionOverflow (by default the reader's, set_read_type;
+        a row reader keeps what held at its creation)."""
         return RowReader(self, include=include, offset=offset, length=length, lazy_dictionary=lazy_dictionary,
-                         tight_numeric=tight_numeric, timezone=timezone)
+                         tight_numeric=tight_numeric, timezone=timezone, read_type=read_type,
+                         throw_on_overflow=throw_on_overflow)
 
     def last_timings(self):
         t = (ctypes.c_double * 5)()
@@ -509,8 +553,8 @@ _TIGHT = {BOOLEAN: np.int8, BYTE: np.int8, SHORT: np.int16, INT: np.int32, FLOAT
 class RowBatch(Batch):
     """A batch of at most `capacity` rows (RowReader::createRowBatch)."""
 
-    def __init__(self, reader, capacity):
-        super().__init__(reader, {})
+    def __init__(self, reader, capacity, types=None):
+        super().__init__(reader, {}, types)
         self.capacity = capacity
         self.num_elements = 0
 
@@ -528,11 +572,29 @@ class RowReader:
     selects the stripes whose offset falls in the byte range (:337-345)."""
 
     def __init__(self, reader, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False,
-                 timezone=None):
+                 timezone=None, read_type=_KEEP, throw_on_overflow=_KEEP):
         if reader._ctx is None:
             raise _lib.InvalidArgument("reader was opened without a device context")
         self.reader = reader
         self._L = reader._L
+        # the row reader copies the reader's read type and overflow rule at
+        # creation: options given here are set for the creation and put back
+        saved = (reader._read_type, reader._throw_on_overflow)
+        try:
+            if read_type is not _KEEP or throw_on_overflow is not _KEEP:
+                reader.set_read_type(saved[0] if read_type is _KEEP else read_type,
+                                     saved[1] if throw_on_overflow is _KEEP else throw_on_overflow)
+            self.types = reader.read_types
+            self._create(reader, include, offset, length, lazy_dictionary, timezone)
+        finally:
+            if (reader._read_type, reader._throw_on_overflow) != saved:
+                reader.set_read_type(*saved)
+        self.tight_numeric = tight_numeric
+        self.lazy_dictionary = bool(lazy_dictionary)
+        self._dicts = {}  # the current stripe's dictionaries (host copies)
+        self._dict_stripe = None
+
+    def _create(self, reader, include, offset, length, lazy_dictionary, timezone):
         opts = _lib.RowReaderOptions()
         opts.offset = offset
         opts.length = (1 << 64) - 1 if length is None else length
@@ -549,10 +611,6 @@ class RowReader:
         h = ctypes.c_void_p()
         check(self._L.orcg_row_reader_create(reader._h, ctypes.byref(opts), ctypes.byref(h)), reader._err)
         self._h = h
-        self.tight_numeric = tight_numeric
-        self.lazy_dictionary = bool(lazy_dictionary)
-        self._dicts = {}  # the current stripe's dictionaries (host copies)
-        self._dict_stripe = None
 
     def _err(self):
         return self._L.orcg_row_reader_last_error(self._h)
@@ -570,7 +628,7 @@ class RowReader:
         self.close()
 
     def create_row_batch(self, capacity):
-        return RowBatch(self.reader, int(capacity))
+        return RowBatch(self.reader, int(capacity), self.types)
 
     def next(self, batch):
         """RowReader::next: True with batch.num_elements rows, False at the end."""
@@ -584,7 +642,7 @@ class RowReader:
         if stripe != self._dict_stripe:
             self._dicts, self._dict_stripe = {}, stripe
         begins = {}
-        for t in self.reader.types:
+        for t in self.types:
             v = _lib.ColumnView()
             b, c = ctypes.c_uint64(), ctypes.c_uint64()
             check(self._L.orcg_row_reader_column(self._h, t.id, ctypes.byref(v), ctypes.byref(b), ctypes.byref(c)),
@@ -600,7 +658,7 @@ class RowReader:
                 begins[t.id] = b.value
         # union offsets index the stripe's child rows: make them batch-relative
         for tid, col in batch.columns.items():
-            t = self.reader.types[tid]
+            t = self.types[tid]
             if t.kind == UNION and col.num_elements:
                 offs = col.offsets.copy()
                 for k, st in enumerate(t.subtypes):

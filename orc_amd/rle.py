@@ -82,6 +82,10 @@ class Context:
     def last_error(self):
         return self._L.orcg_ctx_last_error(self._h)
 
+    def last_error_value(self):
+        """Value index (row) of the last device-side error collected."""
+        return int(self._L.orcg_ctx_last_error_value(self._h))
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.orcg_ctx_destroy(self._h)
@@ -487,6 +491,45 @@ def decimal_decode_device(ctx, src, scales, nvalues, precision, scale, out, src_
     check(L.orcg_decimal_decode_device(ctx.handle, _tensor_ptr(src), n, _tensor_ptr(scales), nvalues, precision,
                                        scale, _tensor_ptr(out)), ctx.last_error)
     return out
+
+
+CONVERT_INT64, CONVERT_FLOAT, CONVERT_DOUBLE, CONVERT_DECIMAL64, CONVERT_DECIMAL128 = range(5)
+
+
+def convert_column_device(ctx, src, src_class, target_kind, precision=0, scale=0, src_scale=0, not_null=None,
+                          throw_on_overflow=False):
+    """Schema evolution of one decoded column on device tensors (the
+    reference's ConvertColumnReader rules): `src` holds the values of class
+    `src_class` (CONVERT_*: int64, float64 holding floats, float64, int64
+    decimals, int64 [n, 2] = [hi, lo] decimals), `target_kind` is the read
+    type's Type.Kind with `precision` / `scale` for a decimal. Returns (data,
+    not_null, nulled): int64 / float64 / int64 [n, 2] values, the new uint8
+    mask (the incoming one is only read) and the number of rows the conversion
+    turned into NULLs; their slots hold 0. With throw_on_overflow the first
+    such row raises instead."""
+    import torch
+
+    L = _lib.load()
+    n = src.shape[0]
+    # the kernel reads 8 (16: Decimal128) bytes a row and one mask byte
+    want_dtype = torch.float64 if src_class in (CONVERT_FLOAT, CONVERT_DOUBLE) else torch.int64
+    want_shape = (n, 2) if src_class == CONVERT_DECIMAL128 else (n,)
+    if src.dtype != want_dtype or tuple(src.shape) != want_shape or not src.is_contiguous():
+        raise InvalidArgument("source tensor does not match its class: want %s %s" % (want_dtype, want_shape))
+    if not_null is not None and (not_null.dtype != torch.uint8 or tuple(not_null.shape) != (n,)
+                                 or not not_null.is_contiguous()):
+        raise InvalidArgument("not_null must be a contiguous uint8 tensor of one byte a row")
+    wide = target_kind == 14 and precision > 18
+    fp = target_kind in (5, 6)
+    out = torch.empty((n, 2) if wide else (n,), dtype=torch.float64 if fp else torch.int64, device=src.device)
+    out_nn = torch.empty(n, dtype=torch.uint8, device=src.device)
+    nulled = ctypes.c_uint64(0)
+    ctx.after_torch()
+    check(L.orcg_convert_column_device(ctx.handle, _tensor_ptr(src), int(src_class), int(src_scale), n,
+                                       None if not_null is None else _tensor_ptr(not_null), int(target_kind),
+                                       int(precision), int(scale), int(bool(throw_on_overflow)), _tensor_ptr(out),
+                                       _tensor_ptr(out_nn), ctypes.byref(nulled)), ctx.last_error)
+    return out, out_nn, int(nulled.value)
 
 
 def timestamp_decode_device(ctx, seconds, nanos, epoch=1420070400):
