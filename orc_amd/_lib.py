@@ -220,6 +220,51 @@ SIGNATURES += [
      i32),
 ]
 
+# include/orcg_arrow.h
+i64 = ctypes.c_int64
+SIGNATURES += [
+    ("orcg_arrow_validity_device", [vp, vp, u64, vp, u64, ctypes.POINTER(u64)], i32),
+    ("orcg_arrow_fixed_device", [vp, i32, vp, vp, u64, vp, u64], i32),
+    ("orcg_arrow_offsets_device", [vp, vp, vp, vp, u64, vp, u64], i32),
+    ("orcg_arrow_dict_strings_device", [vp, i32, vp, vp, u64, vp, u64, vp, u64, vp, u64, vp, u64,
+                                        ctypes.POINTER(u64)], i32),
+    ("orcg_arrow_bench", [vp, i32, i32, vp, vp, vp, vp, u64, u64, u64, vp, u64, u64, ctypes.c_uint32,
+                          ctypes.POINTER(ctypes.c_double)], i32),
+    ("orcg_reader_arrow_schema", [vp, i32, vp], i32),
+    ("orcg_reader_export_arrow_device", [vp, i32, vp], i32),
+    ("orcg_reader_export_arrow_host", [vp, i32, vp], i32),
+]
+
+
+class ArrowSchema(ctypes.Structure):
+    """struct ArrowSchema (Arrow C Data interface)."""
+
+
+ArrowSchema._fields_ = [("format", cp), ("name", cp), ("metadata", cp), ("flags", i64), ("n_children", i64),
+                        ("children", ctypes.POINTER(ctypes.POINTER(ArrowSchema))),
+                        ("dictionary", ctypes.POINTER(ArrowSchema)),
+                        ("release", ctypes.CFUNCTYPE(None, ctypes.POINTER(ArrowSchema))), ("private_data", vp)]
+
+
+class ArrowArray(ctypes.Structure):
+    """struct ArrowArray (Arrow C Data interface)."""
+
+
+ArrowArray._fields_ = [("length", i64), ("null_count", i64), ("offset", i64), ("n_buffers", i64), ("n_children", i64),
+                       ("buffers", ctypes.POINTER(vp)), ("children", ctypes.POINTER(ctypes.POINTER(ArrowArray))),
+                       ("dictionary", ctypes.POINTER(ArrowArray)),
+                       ("release", ctypes.CFUNCTYPE(None, ctypes.POINTER(ArrowArray))), ("private_data", vp)]
+
+
+class ArrowDeviceArray(ctypes.Structure):
+    """struct ArrowDeviceArray (Arrow C Device Data interface)."""
+
+    _fields_ = [("array", ArrowArray), ("device_id", i64), ("device_type", ctypes.c_int32), ("sync_event", vp),
+                ("reserved", i64 * 3)]
+
+
+ARROW_DEVICE_ROCM = 10
+
 
 def load():
     """Load liborcgpu.so (building it first if absent). torch is imported

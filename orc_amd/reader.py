@@ -537,6 +537,93 @@ class Reader:
         kernel instance (default) or one launch per stream."""
         check(self._L.orcg_reader_set_stream_batching(self._h, int(bool(on))), self._err)
 
+    # ---- Arrow export (include/orcg_arrow.h). pyarrow is imported lazily:
+    # the package imports without it.
+
+    def arrow_schema(self, dictionary=False):
+        """The pyarrow.Schema of the selected columns (under a read type, of
+        the read kinds): pyarrow.orc.ORCFile(f).schema for the same file.
+        Needs no GPU. dictionary=True: string columns that are
+        dictionary-encoded in the stripe last decoded come as
+        dictionary<int32, string>."""
+        import pyarrow as pa
+
+        s = _lib.ArrowSchema()
+        check(self._L.orcg_reader_arrow_schema(self._h, int(bool(dictionary)), ctypes.byref(s)), self._err)
+        return pa.Schema._import_from_c(ctypes.addressof(s))  # (moves the schema: released by pyarrow)
+
+    def read_stripe_arrow(self, i, dictionary=False):
+        """Decode stripe i on the GPU, re-lay it as Arrow arrays in HBM and
+        copy those to the host: a pyarrow.RecordBatch equal to
+        pyarrow.orc.ORCFile.read_stripe(i). dictionary=True: string columns
+        dictionary-encoded in this stripe stay dictionary<int32, string>."""
+        import pyarrow as pa
+
+        self.read_stripe_device(i)
+        a, s = _lib.ArrowArray(), _lib.ArrowSchema()
+        check(self._L.orcg_reader_export_arrow_host(self._h, int(bool(dictionary)), ctypes.byref(a)), self._err)
+        rc = self._L.orcg_reader_arrow_schema(self._h, int(bool(dictionary)), ctypes.byref(s))
+        if rc:
+            a.release(ctypes.byref(a))
+            check(rc, self._err)
+        return pa.RecordBatch._import_from_c(ctypes.addressof(a), ctypes.addressof(s))
+
+    def read_arrow(self):
+        """Every stripe as one pyarrow.Table (pyarrow.orc.ORCFile.read()),
+        stripe by stripe."""
+        import pyarrow as pa
+
+        schema = self.arrow_schema()
+        return pa.Table.from_batches([self.read_stripe_arrow(i) for i in range(self.num_stripes)], schema=schema)
+
+    def arrow_device_buffers(self, dictionary=False):
+        """The device export of the stripe last decoded
+        (orcg_reader_export_arrow_device), flattened depth first: a list of
+        (path, buffer index, device pointer or None, bytes) in the order
+        pyarrow's Array.buffers() lists them, the payload bytes without the
+        padding; plus the export's (device_type, device_id). The pointers stay
+        valid until the reader's next read."""
+        d, s = _lib.ArrowDeviceArray(), _lib.ArrowSchema()
+        check(self._L.orcg_reader_export_arrow_device(self._h, int(bool(dictionary)), ctypes.byref(d)), self._err)
+        rc = self._L.orcg_reader_arrow_schema(self._h, int(bool(dictionary)), ctypes.byref(s))
+        if rc:
+            d.array.release(ctypes.byref(d.array))
+            check(rc, self._err)
+        out = []
+        try:
+            self._arrow_walk(s, d.array, "", out)
+        finally:
+            d.array.release(ctypes.byref(d.array))
+            s.release(ctypes.byref(s))
+        return out, (d.device_type, d.device_id)
+
+    _ARROW_WIDTH = {b"c": 1, b"s": 2, b"i": 4, b"l": 8, b"f": 4, b"g": 8}
+
+    def _arrow_walk(self, s, a, path, out):
+        fmt, n = s.format, a.length
+        bufs = [a.buffers[k] for k in range(a.n_buffers)]
+        sizes = [(n + 7) // 8 if bufs and bufs[0] else 0]
+        if fmt in (b"u", b"z", b"+l", b"+m"):
+            sizes.append(4 * (n + 1))
+            if fmt in (b"u", b"z"):
+                last = self._host(bufs[1] + 4 * n, 4, np.int32)
+                sizes.append(int(last[0]))
+        elif fmt == b"b":
+            sizes.append((n + 7) // 8)
+        elif fmt in self._ARROW_WIDTH:
+            sizes.append(self._ARROW_WIDTH[fmt] * n)
+        elif fmt.startswith(b"d:"):
+            sizes.append(16 * n)
+        elif fmt.startswith(b"t"):
+            sizes.append(4 * n if fmt == b"tdD" else 8 * n)
+        for k, (p, size) in enumerate(zip(bufs, sizes)):
+            out.append((path, k, p, size))
+        if s.dictionary:
+            self._arrow_walk(s.dictionary.contents, a.dictionary.contents, path + "/dictionary", out)
+        for k in range(a.n_children):
+            c = s.children[k].contents
+            self._arrow_walk(c, a.children[k].contents, path + "/" + c.name.decode(), out)
+
     def read(self, fields=None):
         """All rows as dicts of the root struct's fields (pyarrow to_pylist shape)."""
         rows = []
