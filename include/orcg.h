@@ -238,6 +238,14 @@ int orcg_byterle_decode_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src
 int orcg_boolrle_decode_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src_len,
                                const orcg_segment* d_segs, uint64_t nsegs, uint64_t row_begin,
                                uint64_t nrows, uint8_t* d_dst);
+/* The same decode with what the file reader passes along: d_nrows (device,
+ * may be NULL) holds the row count, read by the kernel, with nrows the
+ * host-side bound of it (the size of d_dst); the decode adds the number of
+ * set rows it writes to *d_ones (device, may be NULL; not zeroed here). */
+int orcg_boolrle_decode_counted_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src_len,
+                                       const orcg_segment* d_segs, uint64_t nsegs, uint64_t row_begin,
+                                       uint64_t nrows, const uint64_t* d_nrows, uint8_t* d_dst,
+                                       uint64_t* d_ones);
 
 /* Stateful drop-in for orc::ByteRleDecoder as created by
  * createByteRleDecoder / createBooleanRleDecoder (c++/src/ByteRLE.hh:114,126):

@@ -12,6 +12,7 @@ from .rle import (  # noqa: F401
     Context,
     Plan,
     RleDecoderV2,
+    boolrle_decode_counted_device,
     RleVersion_1,
     RleVersion_2,
     byterle_decode_device,

@@ -87,6 +87,7 @@ SIGNATURES = [
     ("orcg_byterle_plan_create", [vp, u64, u64, u64, ctypes.POINTER(vp)], i32),
     ("orcg_byterle_decode_device", [vp, vp, u64, vp, u64, u64, u64, vp], i32),
     ("orcg_boolrle_decode_device", [vp, vp, u64, vp, u64, u64, u64, vp], i32),
+    ("orcg_boolrle_decode_counted_device", [vp, vp, u64, vp, u64, u64, u64, vp, vp, vp], i32),
     ("orcg_byte_rle_decoder_create", [vp, vp, u64, i32, ctypes.POINTER(vp)], i32),
     ("orcg_byte_rle_decoder_destroy", [vp], None),
     ("orcg_byte_rle_decoder_next", [vp, vp, u64, vp], i32),

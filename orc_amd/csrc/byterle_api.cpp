@@ -25,7 +25,13 @@ orcg_rlev2_plan* make_byte_plan(const uint8_t* src, uint64_t len, uint64_t max_b
     const uint32_t h = src[pos];
     const uint64_t L = h < 0x80 ? h + 3 : 256 - h;
     const uint64_t bytes = h < 0x80 ? 2 : 1 + L;
-    if (pos + bytes > len) {  // truncated group: the read fails here
+    if (pos + bytes > len) {
+      // truncated group: a run fails at its first value (readHeader reads the
+      // value byte); a literal hands out the bytes that are there and fails at
+      // the first missing one (nextInternal, ByteRLE.cc:484-494)
+      const uint64_t have = h < 0x80 ? 0 : len - pos - 1;
+      if (have && (!open || pos - seg_b >= max_bytes || vi - seg_v >= max_values)) p->segs.push_back({pos, vi});
+      vi += have;
       p->err = kErrByteBadRead;
       p->err_at = vi;
       break;
@@ -204,6 +210,15 @@ int orcg_boolrle_decode_device(orcg_ctx* c, const uint8_t* d_src, uint64_t src_l
   if (!c || (nsegs && (!d_src || !d_segs)) || (nrows && !d_dst)) return ORCG_INVALID_ARGUMENT;
   (void)hipSetDevice(c->device);
   return launch_byterle(c, d_src, src_len, (const uint64_t*)d_segs, nsegs, true, row_begin, nrows, d_dst, nullptr);
+}
+
+int orcg_boolrle_decode_counted_device(orcg_ctx* c, const uint8_t* d_src, uint64_t src_len,
+                                       const orcg_segment* d_segs, uint64_t nsegs, uint64_t row_begin, uint64_t nrows,
+                                       const uint64_t* d_nrows, uint8_t* d_dst, uint64_t* d_ones) {
+  if (!c || (nsegs && (!d_src || !d_segs)) || (nrows && !d_dst)) return ORCG_INVALID_ARGUMENT;
+  (void)hipSetDevice(c->device);
+  return launch_byterle(c, d_src, src_len, (const uint64_t*)d_segs, nsegs, true, row_begin, nrows, d_dst, d_ones,
+                        d_nrows);
 }
 
 int orcg_byte_rle_decoder_create(orcg_ctx* c, const uint8_t* src, uint64_t len, int boolean,

@@ -271,7 +271,12 @@ __global__ __launch_bounds__(kBThreads) void byterle_kernel(const uint8_t* __res
         const uint32_t h = chunk_byte(mine, p - cs);
         const uint32_t gl = group_len(h), L = group_dec(h);
         if ((uint64_t)p + gl > src_left) {
-          report(err, di, kErrByteBadRead);
+          // a run without its value byte fails at its first value
+          // (readHeader); a cut literal hands out the bytes that are there
+          // and fails at the first missing one, if that one is asked for
+          // (nextInternal reads a literal's bytes as it copies them)
+          const uint64_t bad = h < 0x80 ? di : di + (src_left - p - 1);
+          if (bad < vend) report(err, bad, kErrByteBadRead);
           s_ctl[2] = 1;
           break;
         }

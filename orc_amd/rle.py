@@ -454,6 +454,21 @@ def byterle_decode_device(ctx, src, segments, nvalues, out, value_begin=0, boole
     return out
 
 
+def boolrle_decode_counted_device(ctx, src, segments, nrows, out, row_begin=0, row_count=None, ones=None):
+    """Boolean RLE decode as the file reader launches it: `row_count` (a
+    uint64 / int64 device tensor of one element, or None) holds the number of
+    rows, at most the host-side bound `nrows`; the number of set rows written
+    is added to `ones` (the same kind of tensor, or None)."""
+    L = _lib.load()
+    ctx.after_torch()
+    check(L.orcg_boolrle_decode_counted_device(ctx.handle, _tensor_ptr(src), src.numel(), _tensor_ptr(segments),
+                                               segments.shape[0], row_begin, nrows,
+                                               None if row_count is None else _tensor_ptr(row_count),
+                                               _tensor_ptr(out), None if ones is None else _tensor_ptr(ones)),
+          ctx.last_error)
+    return out
+
+
 def scatter_not_null_device(ctx, dense, not_null, out, fill=None):
     """dense values -> non-null rows of out (null slots untouched, or `fill`)."""
     L = _lib.load()

@@ -63,7 +63,7 @@ def orc_file(body, stripes, types, num_rows, footer_length_override=None, row_in
 # Footer", "Type Information")
 PRESENT, DATA, LENGTH, DICTIONARY_DATA, SECONDARY, ROW_INDEX = 0, 1, 2, 3, 5, 6
 ENC_DIRECT, ENC_DICTIONARY, ENC_DIRECT_V2, ENC_DICTIONARY_V2 = 0, 1, 2, 3
-T_SHORT, T_INT, T_LONG, T_STRING, T_STRUCT, T_DECIMAL = 2, 3, 4, 7, 12, 14
+T_BOOLEAN, T_BYTE, T_SHORT, T_INT, T_LONG, T_STRING, T_STRUCT, T_DECIMAL = 0, 1, 2, 3, 4, 7, 12, 14
 
 
 def stream_msg(kind, column, length):

@@ -225,8 +225,6 @@ def test_boolean_segments_of_every_size(orc, null_frac, seg_bytes):
     shorter than a window, several windows per segment, one segment for the
     whole stream) on PRESENT-shaped data, plus the set-row count the file
     reader takes its non-null counts from."""
-    import ctypes
-
     import torch
 
     rng = np.random.default_rng(int(null_frac * 100) + seg_bytes % 97)
@@ -242,18 +240,40 @@ def test_boolean_segments_of_every_size(orc, null_frac, seg_bytes):
     orc.byterle_decode_device(ctx, src, segs, n, out, boolean=True)
     ctx.synchronize()
     np.testing.assert_array_equal(out.cpu().numpy(), full[:n])
+    # the set-row count: added to a counter that is not zero, for the whole
+    # column and for a range that starts and ends inside decoded bytes
+    for a, b in [(0, n), (4_099, n - 13)]:
+        ones = torch.tensor([77], dtype=torch.int64, device="cuda")
+        out = torch.zeros(b - a, dtype=torch.uint8, device="cuda")
+        orc.boolrle_decode_counted_device(ctx, src, segs, b - a, out, row_begin=a, ones=ones)
+        ctx.synchronize()
+        np.testing.assert_array_equal(out.cpu().numpy(), full[a:b])
+        assert int(ones.cpu()[0]) == 77 + int(bits[a:b].sum())
     # decoded bytes (non-boolean) at an offset range
     outb = torch.zeros(len(raw) - 5, dtype=torch.uint8, device="cuda")
     orc.byterle_decode_device(ctx, src, segs, len(raw) - 5, outb, value_begin=5)
     ctx.synchronize()
     np.testing.assert_array_equal(outb.cpu().numpy(), np.frombuffer(raw, dtype=np.uint8)[5:])
-    del ctypes
+
+
+def _oracle_count(data, upper):
+    """Values the oracle hands out before it fails: the largest k <= upper
+    for which a fresh decoder's next(k) succeeds."""
+    lo, hi = 0, upper
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        try:
+            oracle.ByteRleDecoder(data, boolean=False).next(mid)
+            lo = mid
+        except oracle.OracleError:
+            hi = mid - 1
+    return lo
 
 
 def test_truncated_stream_reports_first_bad_group(orc):
-    """A stream cut inside a literal group: the reference's "bad read in
-    nextBuffer" is raised for the first value of that group, whichever
-    thread of the window finds it."""
+    """A cut stream: the reference's "bad read in nextBuffer", after the
+    values the reference hands out (a cut literal's bytes that are there
+    among them), whichever thread of the window finds the cut."""
     rng = np.random.default_rng(3)
     raw = random_bytes(rng, 30_000)
     enc = byte_rle_encode(raw, rng)
@@ -266,6 +286,13 @@ def test_truncated_stream_reports_first_bad_group(orc):
         with pytest.raises(orc.ParseError) as ge:
             gd.next(len(raw))
         assert "bad read in nextBuffer" in str(ge.value) and str(we.value) in str(ge.value)
+        k = _oracle_count(bad, len(raw))
+        assert 0 < k < len(raw)
+        want = oracle.ByteRleDecoder(bad, boolean=False).next(k)
+        np.testing.assert_array_equal(want, np.frombuffer(raw, dtype=np.uint8)[:k])
+        np.testing.assert_array_equal(orc.ByteRleDecoder(bad, boolean=False).next(k), want, "cut %d" % cut)
+        with pytest.raises(orc.ParseError, match="bad read in nextBuffer"):
+            orc.ByteRleDecoder(bad, boolean=False).next(k + 1)
 
 
 @pytest.mark.parametrize("n,p_null", [(1, 0.0), (4095, 0.5), (4097, 1.0), (1_000_003, 0.0), (9_000_011, 0.37),
