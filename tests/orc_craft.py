@@ -151,3 +151,47 @@ def struct_file(names, kinds, stripes, row_index_stride):
     types = [type_msg(T_STRUCT, list(range(1, len(names) + 1)), names)]
     types += [k if isinstance(k, bytes) else type_msg(k) for k in kinds]
     return orc_file(body, infos, types, total, row_index_stride=row_index_stride)
+
+
+# ---- whole files: an arbitrary type tree ------------------------------------------
+T_LIST, T_MAP, T_UNION = 10, 11, 13
+
+
+def tree_stripe(columns, groups):
+    """(index section, data section, stripe footer) of a stripe whose columns
+    (CraftColumn per type id, the root first; any may carry a PRESENT stream
+    among its streams) are written in type-id order. groups: the row groups of
+    the row index (0: no index section); a column's positions hold one list
+    per row group (None: entries without positions, as a struct without a
+    PRESENT stream has), in the order the readers consume them: PRESENT's
+    byte offset, bytes to skip and bits to skip, then the kind's streams."""
+    index, data, sf = b"", b"", b""
+    if groups:
+        for cid, c in enumerate(columns):
+            entries = [[]] * groups if c.positions is None else [[int(p) for p in e] for e in c.positions]
+            assert len(entries) == groups, (cid, len(entries), groups)
+            m = row_index_msg(entries)
+            index += m
+            sf += field_bytes(1, stream_msg(ROW_INDEX, cid, len(m)))
+    for cid, c in enumerate(columns):
+        for kind, b in c.streams:
+            data += b
+            sf += field_bytes(1, stream_msg(kind, cid, len(b)))
+    for c in columns:
+        sf += field_bytes(2, encoding_msg(c.encoding, c.dictionary_size))
+    return index, data, sf
+
+
+def tree_file(types, stripes, row_index_stride):
+    """An uncompressed file of the type tree `types` (Type messages in type-id
+    order, type_msg) with stripes = [(num_rows, [CraftColumn per type id])];
+    the row groups are row_index_stride top-level rows each (0: no index)."""
+    body, infos, total = b"", [], 0
+    for num_rows, columns in stripes:
+        assert len(columns) == len(types)
+        groups = (num_rows + row_index_stride - 1) // row_index_stride if row_index_stride else 0
+        index, data, sf = tree_stripe(columns, groups)
+        infos.append(stripe_info(3 + len(body), len(index), len(data), len(sf), num_rows))
+        body += index + data + sf
+        total += num_rows
+    return orc_file(body, infos, types, total, row_index_stride=row_index_stride)
