@@ -15,6 +15,7 @@ from .rle import (  # noqa: F401
     boolrle_decode_counted_device,
     RleVersion_1,
     RleVersion_2,
+    V1Plan,
     byterle_decode_device,
     convert_column_device,
     create_boolean_rle_decoder,

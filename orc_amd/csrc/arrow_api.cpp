@@ -8,7 +8,7 @@ using namespace orcg::arrow;
 
 namespace {
 
-// The entries' small device block (scratch slot 3): [0] the export's error
+// The entries' small device block (kScratchNotNull): [0] the export's error
 // word, [1] a null count, [2] a scan total.
 struct Block {
   unsigned long long* d = nullptr;
@@ -17,7 +17,7 @@ struct Block {
 
 int block_init(Ctx* c, Block* b) {
   void* p;
-  int rc = scratch(c, 3, sizeof b->h, &p);
+  int rc = scratch(c, kScratchNotNull, sizeof b->h, &p);
   if (rc) return rc;
   b->d = (unsigned long long*)p;
   return hip_check(c, hipMemcpyAsync(b->d, b->h, sizeof b->h, hipMemcpyHostToDevice, c->stream), "H2D export block");
@@ -42,8 +42,8 @@ int block_error(Ctx* c, const Block& b) {
 int scan_rows(Ctx* c, const int64_t* d_lengths, const int64_t* d_index, const int64_t* d_dict_offsets,
               uint64_t dict_size, const uint8_t* d_nn, uint64_t n, Block& b, int64_t** scan) {
   void *lens = nullptr, *sc = nullptr;
-  int rc = scratch(c, 2, 8 * std::max<uint64_t>(n, 1), &lens);
-  if (!rc) rc = scratch(c, 4, 8 * (n + 1), &sc);
+  int rc = scratch(c, kScratchDense, 8 * std::max<uint64_t>(n, 1), &lens);
+  if (!rc) rc = scratch(c, kScratchColumn, 8 * (n + 1), &sc);
   if (!rc) rc = launch_row_lengths(c, d_lengths, d_index, d_dict_offsets, dict_size, d_nn, n, (int64_t*)lens, b.d);
   if (!rc) rc = launch_exclusive_scan(c, (const int64_t*)lens, n, (int64_t*)sc, nullptr, (uint64_t*)(b.d + 2));
   *scan = (int64_t*)sc;

@@ -677,13 +677,13 @@ struct alignas(16) Pair128 {
   __host__ __device__ explicit Pair128(int64_t f) : hi(f < 0 ? -1 : 0), lo(f) {}
 };
 
-// Tile counts of the not-null bytes (scratch slot 5), then their exclusive
-// scan (slot 6: tiles + 1 offsets, the last one the total).
+// Tile counts of the not-null bytes (kScratchTileCounts), then their exclusive
+// scan (kScratchTileOffsets: tiles + 1 offsets, the last one the total).
 static int launch_tile_offsets(Ctx* ctx, const uint8_t* d_nn, uint64_t n, uint64_t tiles, uint64_t** d_off) {
   if (tiles > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many rows");
   void *d_counts, *off;
-  int rc = scratch(ctx, 5, tiles * sizeof(uint32_t), &d_counts);
-  if (!rc) rc = scratch(ctx, 6, (tiles + 1) * sizeof(uint64_t), &off);
+  int rc = scratch(ctx, kScratchTileCounts, tiles * sizeof(uint32_t), &d_counts);
+  if (!rc) rc = scratch(ctx, kScratchTileOffsets, (tiles + 1) * sizeof(uint64_t), &off);
   if (rc) return rc;
   hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)tiles), dim3(kThreads), 0, ctx->stream, d_nn, n,
                      (uint32_t*)d_counts);

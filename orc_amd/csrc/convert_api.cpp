@@ -83,7 +83,7 @@ int orcg_convert_column_device(orcg_ctx* c, const void* d_src, int src_class, in
   if (rc || n == 0) return rc;
   (void)hipSetDevice(c->device);
   void* d_count;
-  if ((rc = scratch(c, 7, sizeof(unsigned long long), &d_count))) return rc;
+  if ((rc = scratch(c, kScratchMisc, sizeof(unsigned long long), &d_count))) return rc;
   if ((rc = hip_check(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), c->stream), "memset"))) return rc;
   a.src = d_src;
   a.nn = d_not_null;
@@ -129,7 +129,7 @@ int orcg_convert_bench(orcg_ctx* c, const void* d_src, int src_class, int32_t sr
   if (rc) return rc;
   (void)hipSetDevice(c->device);
   void* d_count;
-  if ((rc = scratch(c, 7, sizeof(unsigned long long), &d_count))) return rc;
+  if ((rc = scratch(c, kScratchMisc, sizeof(unsigned long long), &d_count))) return rc;
   if ((rc = hip_check(c, hipMemsetAsync(d_count, 0, sizeof(unsigned long long), c->stream), "memset"))) return rc;
   a.src = d_src;
   a.nn = d_not_null;

@@ -15,8 +15,8 @@ static int decimal_decode(orcg_ctx* c, const uint8_t* d_src, uint64_t src_len, c
   (void)hipSetDevice(c->device);
   const uint64_t ntiles_max = src_len / kVarintTile + 2;
   void *d_counts, *d_base;
-  int rc = scratch(c, 5, ntiles_max * sizeof(int64_t), &d_counts);
-  if (!rc) rc = scratch(c, 6, (ntiles_max + 1) * sizeof(int64_t), &d_base);
+  int rc = scratch(c, kScratchTileCounts, ntiles_max * sizeof(int64_t), &d_counts);
+  if (!rc) rc = scratch(c, kScratchTileOffsets, (ntiles_max + 1) * sizeof(int64_t), &d_base);
   if (rc) return rc;
   uint64_t ntiles = 0;
   if ((rc = launch_varint_tile_counts(c, d_src, src_len, (int64_t*)d_counts, &ntiles))) return rc;

@@ -9,35 +9,34 @@
 #include <vector>
 
 #include "../../include/orcg.h"
+#include "host_plan.hh"
 
 namespace orcg {
 
-// Device-side error codes (the low byte of the packed device error record).
-// Messages are the reference's ParseError texts (c++/src/RleDecoderV2.cc).
-enum DevErr : uint32_t {
-  kErrNone = 0,
-  kErrBadRead = 1,         // "bad read in RleDecoderV2::readByte"            :38
-  kErrPatchedPl0 = 2,      // "Corrupt PATCHED_BASE encoded data (pl==0)!"     :307
-  kErrPatchedWidth = 3,    // "... (patchBitSize + pgw > 64)!"                 :328-330
-  kErrDeltaLength = 4,     // "Illegal run length for delta encoding: 1"       :412-415
-  kErrBadSegment = 5,      // positions / segment table not run aligned (InvalidArgument)
-  kErrByteBadRead = 6,     // "bad read in nextBuffer" (ByteRLE.cc:364)
-  kErrDictIndex = 7,       // "Entry index out of range in StringDictionaryColumn" (ColumnReader.cc:578)
-  kErrV1BadRead = 8,       // "bad read in readByte" (RLEv1.cc:141-146)
-  kErrDecimalScale = 9,    // "Decimal scale out of range" (ColumnReader.cc:1348)
-  kErrHive11Overflow = 10, // "Hive 0.11 decimal was more than 38 digits." (ColumnReader.cc:1654)
-  // Java face (RunLengthIntegerReaderV2.java, readPatchedBaseValues :149-260)
-  kErrJavaCorrupt = 11,    // IOException "Corruption in ORC data encountered. ..." (pw + pgw > 64, :196-200)
-  kErrJavaPatchIndex = 12, // ArrayIndexOutOfBoundsException: pl == 0 reads unpackedPatch[0] (:207)
-  // schema evolution (ConvertColumnReader.cc handleOverflow, :66-76); the caller appends the type names
-  kErrConvertOverflow = 13, // "Overflow when convert from <file type> to <read type>"
-};
-
-const char* dev_error_message(uint32_t code);
-int dev_error_status(uint32_t code);
-
 // The device error record: min over (value_index << 8 | code). ~0 = none.
 constexpr unsigned long long kNoError = ~0ull;
+
+// The roles of a context's scratch buffers (scratch()). A buffer holds one
+// thing at a time: a caller must not hold a slot across a launcher that takes
+// it. Launchers that take slots themselves (every other one takes none):
+//   launch_scatter, launch_count_nonzero   kScratchTileCounts, kScratchTileOffsets
+// Callers: the host round trip (host_decode.hh) kScratchStream, kScratchSegments,
+// kScratchDense; the decimal decode kScratchTileCounts, kScratchTileOffsets
+// (its own tiles; it calls neither launcher above); the Arrow export
+// kScratchNotNull (its entry block), kScratchDense, kScratchColumn; the convert
+// entry points kScratchMisc; the debug hooks kScratchDense, kScratchColumn,
+// kScratchMisc.
+enum ScratchSlot {
+  kScratchStream = 0,       // a host stream's bytes
+  kScratchSegments = 1,     // its segment table
+  kScratchDense = 2,        // dense decoded values
+  kScratchNotNull = 3,      // not-null bytes
+  kScratchColumn = 4,       // column output
+  kScratchTileCounts = 5,   // per-tile counts
+  kScratchTileOffsets = 6,  // their scan
+  kScratchMisc = 7,
+  kScratchSlots
+};
 
 struct Ctx {
   int device = 0;
@@ -46,13 +45,9 @@ struct Ctx {
   unsigned long long* d_err = nullptr;  // device error record
   std::string last_error;
   uint64_t last_error_value = 0;
-  // grow-only device scratch
-  // scratch slots: 0 stream, 1 segments, 2 dense values, 3 not-null,
-  // 4 column output, 5 tile counts, 6 tile offsets, 7 misc
-  void* d_scratch[8] = {};
-  size_t scratch_cap[8] = {};
-  void* h_pinned = nullptr;
-  size_t pinned_cap = 0;
+  // grow-only device scratch, one buffer per ScratchSlot
+  void* d_scratch[kScratchSlots] = {};
+  size_t scratch_cap[kScratchSlots] = {};
   int rlev2_variant = ORCG_RLEV2_TILED;  // which RLEv2 kernel to launch
   void* d_defer = nullptr;  // RLEv2 short-run segment queue (rlev2_tiled.hip defer_queue)
   uint64_t defer_cap = 0;
@@ -157,7 +152,7 @@ void* pinned_alloc(size_t bytes, int node = -1);
 int current_numa_node();
 void pinned_free(void* p);
 int hip_check(Ctx* ctx, hipError_t e, const char* what);
-int scratch(Ctx* ctx, int slot, size_t bytes, void** out);
+int scratch(Ctx* ctx, ScratchSlot slot, size_t bytes, void** out);
 // Wait for the context stream and fold the device error record into a status.
 int sync_ctx(Ctx* ctx);
 
@@ -402,14 +397,15 @@ int launch_union_check(Ctx* ctx, const uint8_t* d_tags, uint64_t n, uint32_t nch
 int launch_union_offsets(Ctx* ctx, const uint8_t* d_tags, uint64_t n, uint32_t k, const int64_t* d_scan_k,
                          int64_t* d_offsets);
 
-// Multi-workgroup exclusive scan: d_out[0..n] (n + 1 entries). Scratch 7.
+// Multi-workgroup exclusive scan: d_out[0..n] (n + 1 entries). Takes no scratch slot.
 // d_flags (may be null; zero on entry): StringDirect length checks fused into
 // the scan, [0] |= 1 for a negative input, [1] |= 1 when the total wraps.
 // d_total (may be null): the total (d_out[n]) also written there (e.g. a
 // slot of the reader's read-back block: no separate copy).
 int launch_exclusive_scan(Ctx* ctx, const int64_t* d_in, uint64_t n, int64_t* d_out, uint64_t* d_flags = nullptr,
                           uint64_t* d_total = nullptr);
-// Number of non-zero bytes of d_nn[0..n) into *d_total (device). Scratch 5, 6.
+// Number of non-zero bytes of d_nn[0..n) into *d_total (device).
+// kScratchTileCounts, kScratchTileOffsets.
 int launch_count_nonzero(Ctx* ctx, const uint8_t* d_nn, uint64_t n, uint64_t* d_total);
 // *d_flag = 1 if any d_v[i] < 0, else 0.
 int launch_flag_negative(Ctx* ctx, const int64_t* d_v, uint64_t n, uint64_t* d_flag);
@@ -442,23 +438,3 @@ inline int launch_rlev2(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is
 }  // namespace orcg
 
 struct orcg_ctx : orcg::Ctx {};
-
-// Host run walk result (RLEv2 or byte RLE): segment cuts, decodable values,
-// first corrupt run.
-struct orcg_rlev2_plan {
-  std::vector<orcg_segment> segs;
-  uint64_t values = 0;
-  uint32_t err = orcg::kErrNone;
-  uint64_t err_at = 0;
-};
-
-orcg_rlev2_plan* make_plan(const uint8_t* src, uint64_t len, uint64_t max_bytes, uint64_t max_values, int java = 0);
-namespace orcg {
-// The RLEv2 run at `pos` (host): kErrNone with its value count and end, or a DevErr.
-uint32_t host_parse_run(const uint8_t* s, uint64_t len, uint64_t pos, uint64_t* run_len, uint64_t* run_end);
-}  // namespace orcg
-orcg_rlev2_plan* make_v1_plan(const uint8_t* src, uint64_t len, uint64_t max_bytes, uint64_t max_values);
-orcg_rlev2_plan* make_byte_plan(const uint8_t* src, uint64_t len, uint64_t max_bytes, uint64_t max_values);
-// H2D + RLEv2 decode of the first `count` values + D2H into host `out`.
-int decode_host_dense(orcg::Ctx* c, const uint8_t* src, uint64_t len, int is_signed,
-                      const orcg_rlev2_plan* plan, uint64_t count, void* out, int width, int java = 0);

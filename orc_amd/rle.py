@@ -241,12 +241,15 @@ def rlev1_decode(data, n, is_signed, not_null=None, dtype=np.int64, ctx=None, ou
 
 class Plan:
     """orcg_rlev2_plan: host run walk -> segments (+ first corrupt run)."""
+    _create, _max_values = "orcg_rlev2_plan_create", 8192
 
-    def __init__(self, data, max_segment_bytes=16 << 10, max_segment_values=8192):
+    def __init__(self, data, max_segment_bytes=16 << 10, max_segment_values=None):
         self._L = _lib.load()
         self._buf = np.frombuffer(bytes(data), dtype=np.uint8)
         h = ctypes.c_void_p()
-        check(self._L.orcg_rlev2_plan_create(_ptr(self._buf), self._buf.size, max_segment_bytes,
+        if max_segment_values is None:
+            max_segment_values = self._max_values
+        check(getattr(self._L, self._create)(_ptr(self._buf), self._buf.size, max_segment_bytes,
                                              max_segment_values, ctypes.byref(h)))
         self._h = h
 
@@ -433,14 +436,12 @@ def create_boolean_rle_decoder(data, ctx=None):
 
 class BytePlan(Plan):
     """orcg_byterle_plan_create: control-byte walk -> segments."""
+    _create, _max_values = "orcg_byterle_plan_create", 16384
 
-    def __init__(self, data, max_segment_bytes=16 << 10, max_segment_values=16384):
-        self._L = _lib.load()
-        self._buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        h = ctypes.c_void_p()
-        check(self._L.orcg_byterle_plan_create(_ptr(self._buf), self._buf.size, max_segment_bytes,
-                                               max_segment_values, ctypes.byref(h)))
-        self._h = h
+
+class V1Plan(Plan):
+    """orcg_rlev1_plan_create: RLEv1 group walk -> segments."""
+    _create = "orcg_rlev1_plan_create"
 
 
 def byterle_decode_device(ctx, src, segments, nvalues, out, value_begin=0, boolean=False):

@@ -32,7 +32,7 @@ def ctx():
 
 
 class DebugDictJob(ctypes.Structure):
-    """orcg_debug_dict_job (orc_amd/csrc/orcg_api.cpp)."""
+    """orcg_debug_dict_job (orc_amd/csrc/debug_api.cpp)."""
 
     _fields_ = [("lengths", vp), ("dict_size", u64), ("offsets", vp), ("summary", vp), ("idx", vp), ("nn", vp),
                 ("n", u64), ("start", vp), ("len", vp), ("err", vp)]
