@@ -126,7 +126,12 @@ typedef struct orcg_segment {
  * decompression) and cuts the stream into segments of at most
  * ~max_segment_bytes / max_segment_values. It also finds the first corrupt
  * run, reported lazily by the decoders exactly where the reference would
- * throw (RleDecoderV2.cc:38, :307, :328-330, :412-415). */
+ * throw (RleDecoderV2.cc:38, :307, :328-330, :412-415).
+ * One limit is this library's own: a DELTA run's two base-128 varints must
+ * end within the run's first 64 bytes (two bytes of header and padded
+ * varints of up to 62 bytes together; no writer emits more than 22). A longer
+ * header is reported as "bad read in RleDecoderV2::readByte" at the run's
+ * first value, by the plan and by every device decoder alike. */
 typedef struct orcg_rlev2_plan orcg_rlev2_plan;
 int orcg_rlev2_plan_create(const uint8_t* src, uint64_t src_len, uint64_t max_segment_bytes,
                            uint64_t max_segment_values, orcg_rlev2_plan** out);

@@ -31,6 +31,14 @@ uint64_t varint_end(const uint8_t* s, uint64_t len, uint64_t p) {
   return p < len ? p + 1 : len + 1;
 }
 
+// The same for a DELTA header's varints: no header byte lies kRlev2HdrLim
+// bytes or more past the run's first (parse_run's `lim`, rlev2_device.hh).
+uint64_t header_varint_end(const uint8_t* s, uint64_t len, uint64_t pos, uint64_t p) {
+  const uint64_t lim = std::min<uint64_t>(len, pos + kRlev2HdrLim);
+  while (p < lim && (s[p] & 0x80u)) ++p;
+  return p < lim ? p + 1 : len + 1;
+}
+
 }  // namespace
 
 uint32_t host_parse_run(const uint8_t* s, uint64_t len, uint64_t pos, uint64_t* run_len, uint64_t* run_end,
@@ -76,7 +84,7 @@ uint32_t host_parse_run(const uint8_t* s, uint64_t len, uint64_t pos, uint64_t* 
   const uint32_t W = fbo ? kFbs[fbo] : 0;
   uint64_t q = pos + 2;
   for (int k = 0; k < 2; ++k)
-    if ((q = varint_end(s, len, q)) > len) return kErrBadRead;
+    if ((q = header_varint_end(s, len, pos, q)) > len) return kErrBadRead;
   if (W != 0 && L < 2) {
     if (!java) return kErrDeltaLength;
     L = 2;  // Java (:125-145): the first value, first + deltaBase, no deltas

@@ -228,10 +228,10 @@ __global__ __launch_bounds__(kThreads, kWavesMin) void rlev2_expand_kernel(const
       Run rn = parse_run([&](uint32_t q) { return (uint32_t)hb[q]; }, ~0ull, 32u - sh, is_signed);
       if (rn.err != kErrNone) {
         // a header past the 32 staged bytes (over-long DELTA varints, which
-        // the first kernel accepts up to its 64-byte limit): from the stream
+        // the first kernel accepts up to kRlev2HdrLim bytes): from the stream
         const uint8_t* g = src + xoff[h];
         const uint64_t avail = src_len - xoff[h];
-        rn = parse_run([&](uint32_t q) { return (uint32_t)g[q]; }, avail, 64u, is_signed);
+        rn = parse_run([&](uint32_t q) { return (uint32_t)g[q]; }, avail, kRlev2HdrLim, is_signed);
       }
       s_v[r] = (int32_t)(xv[h] - s0);
       s_meta[r] = rn.kind | (rn.W << 2) | (rn.L << 9);

@@ -159,7 +159,8 @@ __global__ __launch_bounds__(kWave) void rlev2_decode_kernel(
   // runs beyond it are not reported (the reference throws lazily too).
   while (pos < seg_end && vi < value_end) {
     const uint32_t rel = (uint32_t)(pos - bias);
-    if (win.base == 0xffffffffu || rel < win.base || rel + 32 > win.base + 256) {
+    // the window holds the longest header whole (kRlev2HdrLim bytes)
+    if (win.base == 0xffffffffu || rel < win.base || rel + kRlev2HdrLim > win.base + 256) {
       win.base = rel & ~3u;
       win.word = __builtin_amdgcn_raw_buffer_load_b32(rs, win.base + 4u * lane, 0, 0);
     }
@@ -310,7 +311,9 @@ __global__ __launch_bounds__(kWave) void rlev2_decode_kernel(
         uint32_t b;
         do {
           if (q >= src_len) { report(err, vi, kErrBadRead); return; }
-          if ((uint32_t)(q - bias) + 1 > win.base + 256) {  // never for well-formed varints
+          // a header ends inside the run's first kRlev2HdrLim bytes (host_plan.hh:
+          // the one limit of every RLEv2 decoder here), which the window holds
+          if (q - pos >= kRlev2HdrLim) {
             report(err, vi, kErrBadRead);
             return;
           }

@@ -166,7 +166,7 @@ __device__ __forceinline__ u32x3 lds12(const uint32_t* w, uint32_t o) {
 // dword per lane and read back with v_readlane: one LDS round trip per slice
 // instead of one per header byte. kHdrLim bounds how far a header may reach
 // (DELTA's two varints take <= 22 bytes; longer ones are corrupt).
-constexpr uint32_t kHdrLim = 64;
+constexpr uint32_t kHdrLim = kRlev2HdrLim;  // host_plan.hh: the one limit of every RLEv2 decoder
 
 // terminator bits of a dword's bytes (bit i = byte i < 0x80)
 __device__ __forceinline__ uint32_t term4(uint32_t w) {
