@@ -469,6 +469,45 @@ int orcg_rlev2_encode_runs(const int64_t* values, uint64_t n, int is_signed, con
                            const uint32_t* lengths, uint64_t nruns, uint8_t* dst, uint64_t dst_cap,
                            uint64_t* out_len, uint64_t* run_offsets);
 
+/* ---- Snappy chunks inflated on the device ---------------------------------
+ * ORC's block compression cuts a stream into independent chunks (3-byte
+ * headers; ORCv1.md "Compression"). A Snappy chunk states its decompressed
+ * length in its preamble, so a stream is laid out without inflating anything:
+ * the plan is a table of chunks, the device inflates them in one launch.
+ * Offsets are relative to the source / destination buffers of the decode
+ * call. A stored ("original") chunk is a plain copy. */
+#define ORCG_SNAPPY_STORED 1u
+typedef struct orcg_snappy_chunk {
+  uint64_t src_offset, src_bytes; /* the chunk's body (a raw Snappy block, or the stored bytes) */
+  uint64_t dst_offset, dst_bytes; /* its decompressed bytes */
+  uint64_t flags;                 /* ORCG_SNAPPY_STORED */
+} orcg_snappy_chunk;
+
+/* out[0] = bytes of decompressed history a chunk keeps on chip (a copy that
+ * reaches further back reads the output instead), out[1] = threads per chunk. */
+void orcg_snappy_device_info(uint32_t out[2]);
+/* The plan of `len` host bytes holding chunks framed by ORC's 3-byte headers:
+ * one table entry per chunk, sources at their offsets in `src`, destinations
+ * consecutive from 0. A compressed chunk's preamble is read with the host
+ * decoder's two checks ("snappy: bad length", "snappy: output exceeds the
+ * compression block size"; a cut header is "Read past EOF in
+ * DecompressionStream::readBuffer"): ORCG_PARSE_ERROR with the text in
+ * *error (static storage). table (may be null) receives up to `cap` entries;
+ * *nchunks the number of chunks, *total the decompressed bytes. */
+int orcg_snappy_plan(const uint8_t* src, uint64_t len, uint64_t block_size, orcg_snappy_chunk* table, uint64_t cap,
+                     uint64_t* nchunks, uint64_t* total, const char** error);
+/* Inflates the nchunks chunks of `table` (host memory) from the device bytes
+ * d_src[0, src_len) into d_dst[0, dst_len): one launch, synchronous. Chunks
+ * must lie inside the buffers (ORCG_INVALID_ARGUMENT). Nothing outside a
+ * chunk's destination range is written, whatever the input. A corrupt chunk
+ * fails with ORCG_PARSE_ERROR and the host decoder's text ("snappy: truncated
+ * literal", "snappy: literal out of range", "snappy: truncated copy",
+ * "snappy: copy out of range", "snappy: length mismatch"; the latter also
+ * when a preamble disagrees with dst_bytes); orcg_ctx_last_error_value is the
+ * lowest failing chunk's index. */
+int orcg_snappy_decompress_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src_len,
+                                  const orcg_snappy_chunk* table, uint64_t nchunks, uint8_t* d_dst, uint64_t dst_len);
+
 /* (Roofline calibration copies, orcg_probe_copy, live only in the A/B build
  * liborcgpu_ab.so: orc_amd/csrc/probe_kernels.hip.) */
 

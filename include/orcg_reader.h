@@ -156,6 +156,23 @@ int orcg_reader_is_selected(const orcg_reader* r, uint32_t type_id);
 /* RowReaderOptions::setEnableLazyDecoding: dictionary string columns decode to
  * index + dictionary only (StringDictionaryColumnReader::nextEncoded). */
 int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on);
+/* Device decompression (off by default): with it on, a Snappy file's chunks of
+ * the streams the host never walks -- DATA of DIRECT-encoded string / varchar
+ * / char / binary columns, DICTIONARY_DATA, DATA of float / double, DATA of
+ * varint decimals -- are uploaded compressed and inflated by one launch per
+ * stripe ahead of its decodes (orcg_snappy_decompress_device's kernel). Every
+ * other stream (RLE and byte-RLE streams, PRESENT, LENGTH, SECONDARY,
+ * ROW_INDEX) is inflated on the host as before, and so is every stream of a
+ * file with another codec. Results and errors are the same either way: a
+ * corrupt preamble fails the stripe's preparation, a corrupt chunk body fails
+ * the stripe with ORCG_PARSE_ERROR and the host decoder's text, ahead of any
+ * column's error. Row readers created afterwards take the setting with them. */
+int orcg_reader_set_device_decompression(orcg_reader* r, int on);
+/* out[0] = chunks, out[1] = decompressed bytes the last read inflated on the
+ * device, summed over its stripes (0, 0 with the setting off). ReaderMetrics'
+ * DecompressionCall keeps counting every chunk; DecompressionLatencyUs counts
+ * host time only. */
+int orcg_reader_last_device_inflate(const orcg_reader* r, uint64_t out[2]);
 /* RowReaderOptions::forcedScaleOnHive11Decimal / throwOnHive11DecimalOverflow
  * (c++/include/orc/Reader.hh:258-271): Hive 0.11 decimals (precision 0) decode
  * as Decimal128 [hi, lo] values at forced_scale (default 6); a value past 38
@@ -339,7 +356,9 @@ int orcg_reader_set_metrics_timing(orcg_reader* r, int on);
  * kernel instance per stripe instead of one per stream). */
 uint64_t orcg_reader_last_batched_streams(const orcg_reader* r);
 /* Bytes the last read uploaded: decompressed stream bytes plus row-index /
- * plan tables, summed over its stripes. */
+ * plan tables, summed over its stripes. Streams inflated on the device
+ * (orcg_reader_set_device_decompression) count their compressed bytes and
+ * their chunk table. */
 uint64_t orcg_reader_last_stage_bytes(const orcg_reader* r);
 /* Multi-stream batching on (default) / off (one launch per stream; A/B). */
 int orcg_reader_set_stream_batching(orcg_reader* r, int on);

@@ -124,6 +124,9 @@ SIGNATURES = [
                                    u64, vp, vp, vp], i32),
     ("orcg_rlev2_encode_direct", [vp, u64, i32, i32, vp, u64, ctypes.POINTER(u64), u64, vp], i32),
     ("orcg_rlev2_encode_runs", [vp, u64, i32, vp, vp, u64, vp, u64, ctypes.POINTER(u64), vp], i32),
+    ("orcg_snappy_device_info", [ctypes.POINTER(ctypes.c_uint32)], None),
+    ("orcg_snappy_plan", [vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(cp)], i32),
+    ("orcg_snappy_decompress_device", [vp, vp, u64, vp, u64, vp, u64], i32),
 ]
 
 # symbols of the A/B build (liborcgpu_ab.so, ORCG_LIB) only
@@ -206,6 +209,8 @@ SIGNATURES += [
     ("orcg_reader_last_stage_bytes", [vp], u64),
     ("orcg_reader_set_stream_batching", [vp, i32], i32),
     ("orcg_reader_is_selected", [vp, u32], i32),
+    ("orcg_reader_set_device_decompression", [vp, i32], i32),
+    ("orcg_reader_last_device_inflate", [vp, ctypes.POINTER(u64)], i32),
     ("orcg_row_reader_create", [vp, ctypes.POINTER(RowReaderOptions), ctypes.POINTER(vp)], i32),
     ("orcg_row_reader_destroy", [vp], None),
     ("orcg_row_reader_next", [vp, u64, ctypes.POINTER(u64)], i32),

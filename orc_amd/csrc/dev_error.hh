@@ -27,6 +27,13 @@ enum DevErr : uint32_t {
   kErrJavaPatchIndex = 12, // ArrayIndexOutOfBoundsException: pl == 0 reads unpackedPatch[0] (:207)
   // schema evolution (ConvertColumnReader.cc handleOverflow, :66-76); the caller appends the type names
   kErrConvertOverflow = 13, // "Overflow when convert from <file type> to <read type>"
+  // Snappy chunks inflated on the device (inflate_kernels.hip): the texts of the host's
+  // snappy_decompress (orc_file.cpp); the record's index is the chunk's table index
+  kErrSnappyLiteralTruncated = 14,
+  kErrSnappyLiteralRange = 15,
+  kErrSnappyCopyTruncated = 16,
+  kErrSnappyCopyRange = 17,
+  kErrSnappyLength = 18,
 };
 
 inline const char* dev_error_message(uint32_t code) {
@@ -46,6 +53,11 @@ inline const char* dev_error_message(uint32_t code) {
              "hive.exec.orc.skip.corrupt.data to true";
     case kErrJavaPatchIndex: return "Index 0 out of bounds for length 0";
     case kErrConvertOverflow: return "Overflow when convert";
+    case kErrSnappyLiteralTruncated: return "snappy: truncated literal";
+    case kErrSnappyLiteralRange: return "snappy: literal out of range";
+    case kErrSnappyCopyTruncated: return "snappy: truncated copy";
+    case kErrSnappyCopyRange: return "snappy: copy out of range";
+    case kErrSnappyLength: return "snappy: length mismatch";
   }
   return "unknown device error";
 }

@@ -25,7 +25,7 @@ constexpr unsigned long long kNoError = ~0ull;
 // (its own tiles; it calls neither launcher above); the Arrow export
 // kScratchNotNull (its entry block), kScratchDense, kScratchColumn; the convert
 // entry points kScratchMisc; the debug hooks kScratchDense, kScratchColumn,
-// kScratchMisc.
+// kScratchMisc; orcg_snappy_decompress_device kScratchSegments (its chunk table).
 enum ScratchSlot {
   kScratchStream = 0,       // a host stream's bytes
   kScratchSegments = 1,     // its segment table
@@ -422,6 +422,13 @@ struct PublishArgs {
   uint32_t n;
 };
 int launch_publish(Ctx* ctx, const PublishArgs& a, uint64_t* d_dst, uint64_t* d_flag, uint64_t gen);
+
+// Snappy chunks (inflate_kernels.hip): chunk i of d_table (device) inflates
+// d_src + src_offset into d_dst + dst_offset, a wavefront per chunk; the
+// caller has bounded every entry by the buffers. d_err: the launch's error
+// record ((chunk index << 8) | code), null = the context's.
+int launch_snappy_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_snappy_chunk* d_table, uint64_t nchunks,
+                          uint8_t* d_dst, unsigned long long* d_err);
 
 // Dispatch on ctx->rlev2_variant.
 inline int launch_rlev2(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,

@@ -158,6 +158,18 @@ int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on) {
   r->own_lazy = on != 0;
   return ORCG_OK;
 }
+int orcg_reader_set_device_decompression(orcg_reader* r, int on) {
+  if (!r) return ORCG_INVALID_ARGUMENT;
+  std::lock_guard<std::mutex> lk(r->mu);
+  r->own_dev_inflate = on != 0;
+  return ORCG_OK;
+}
+int orcg_reader_last_device_inflate(const orcg_reader* r, uint64_t out2[2]) {
+  if (!r || !out2) return ORCG_INVALID_ARGUMENT;
+  out2[0] = r->last_dev_inflate[0];
+  out2[1] = r->last_dev_inflate[1];
+  return ORCG_OK;
+}
 int orcg_reader_set_hive11_decimal(orcg_reader* r, int32_t forced_scale, int throw_on_overflow) {
   if (!r || forced_scale < 0 || forced_scale > 38) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
@@ -312,7 +324,7 @@ int orcg_reader_read_stripe(orcg_reader* r, uint64_t stripe) {
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
   orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw);
+                          r->own_evo_throw, r->own_dev_inflate);
   return r->read_stripes(stripe, 1);
 }
 
@@ -320,7 +332,7 @@ int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t it
   if (!r || !decode_s || !h2d_s || iters == 0) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
   orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw);
+                          r->own_evo_throw, r->own_dev_inflate);
   if (!r->ctx) return r->fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (stripe >= r->footer.stripes.size()) return r->fail(ORCG_INVALID_ARGUMENT, "stripe index out of range");
   hipSetDevice(r->ctx->device);
@@ -343,7 +355,7 @@ int orcg_reader_read_stripes(orcg_reader* r, uint64_t first, uint64_t count) {
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
   orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw);
+                          r->own_evo_throw, r->own_dev_inflate);
   return r->read_stripes(first, count);
 }
 

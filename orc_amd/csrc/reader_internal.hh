@@ -34,6 +34,7 @@
 #include "../../include/orcg_reader.h"
 #include "orc_file.hh"
 #include "orcg_internal.hh"
+#include "inflate_plan.hh"
 #include "read_type.hh"
 #include "reader_layout.hh"
 #include "timezone.hh"
@@ -173,6 +174,10 @@ struct StreamBuf {
   bool present = false;
   uint64_t host_off = 0;  // offset in staging (== device offset)
   uint64_t len = 0;       // decompressed bytes
+  // inflated on the device (orcg_reader_set_device_decompression): host_off
+  // lies in the stripe's device-only tail, past everything uploaded; staging
+  // holds nothing there, so no host code may read hs.h + host_off
+  bool device_only = false;
   std::unique_ptr<orcg_rlev2_plan> plan;
   uint64_t seg_off = 0;   // offset of the plan's segment table in staging
   // row-index segmentation: per row group {byte offset, values to skip, bits
@@ -253,6 +258,12 @@ struct HostStage {
   // room kept past the prepared bytes for the upload's tail (read-back block
   // and job arena, upload_tail_bytes): upload_and_decode never reallocates
   uint64_t slack = 0;
+  // Snappy streams the device inflates: their chunk table (sources: the
+  // compressed bytes in staging; destinations in the device-only tail
+  // [tail_off, tail_off + tail_bytes) of the stripe's allocation, tail_off >=
+  // used + slack), written to staging at inflate_off
+  std::vector<orcg_snappy_chunk> inflate;
+  uint64_t inflate_off = 0, tail_off = 0, tail_bytes = 0;
   ~HostStage() { pinned_free(h); }
   bool pinned_mapped = false;  // h is hipHostMalloc'd (the device can read it through the same pointer)
   bool ensure(uint64_t bytes, uint64_t keep) {
@@ -309,7 +320,8 @@ struct EvPair {
 // What upload_and_decode appends to a stripe's staging for nc columns: the
 // read-back block (error records, non-null counts, summary slots) and the
 // job arena of the batched launches, each 256-byte aligned.
-inline uint64_t rb_words_for(size_t nc) { return 2 * nc + 1 + 4 * nc + 16; }
+// (+ 1: the stripe's device inflate record)
+inline uint64_t rb_words_for(size_t nc) { return 2 * nc + 1 + 4 * nc + 16 + 1; }
 inline uint64_t arena_bytes_for(size_t nc, uint64_t v1_segs, uint64_t dict_tiles) {
   // (dictionary jobs: one copy per 2,048-row tile of a column)
   return 5 * (nc + 1) * sizeof(RleJob) + (nc + 1) * sizeof(DictJob) * dict_tiles + v1_segs * sizeof(V1SegDesc) +
@@ -347,6 +359,11 @@ struct orcg_reader {
   Ctx* own_ctx = nullptr;
   std::vector<uint8_t> own_sel;  // per type id
   bool own_lazy = false;
+  // orcg_reader_set_device_decompression: Snappy chunks of raw byte streams
+  // ride the upload compressed and inflate on the device. The reader's own,
+  // and that of the decode in progress (a row reader's copy)
+  bool own_dev_inflate = false, dev_inflate = false;
+  uint64_t last_dev_inflate[2] = {0, 0};  // last read: chunks, decompressed bytes inflated on the device
   // The options of the decode in progress (valid under mu, set by Active):
   // the reader's own for its reads, a row reader's for that row reader's
   // prefetch decodes.
@@ -377,8 +394,9 @@ struct orcg_reader {
   struct Active {
     orcg_reader* r;
     Active(orcg_reader* r_, Ctx* c, const std::vector<uint8_t>& sel, bool lazy, const ZoneEntry* rtz,
-           const std::string& ltz, std::shared_ptr<const ReadPlan> rd, bool evo)
+           const std::string& ltz, std::shared_ptr<const ReadPlan> rd, bool evo, bool dev_inflate)
         : r(r_) {
+      r->dev_inflate = dev_inflate;
       r->read = std::move(rd);
       r->evo_throw = evo;
       r->ctx = c;
@@ -480,6 +498,7 @@ struct orcg_reader {
     // the read-back block's pinned mirror (valid after the stripe's copy)
     uint64_t* h_rb = nullptr;
     size_t h_rb_cap = 0, rb_words = 0, rb_used = 0;
+    size_t inflate_word = 0;  // the device inflate's error record in the read-back block (0: none)
     std::vector<EvPair> ev_used;  // metrics timing events
     hipEvent_t done = nullptr;    // recorded after the read-back copy
     // GPU-time split of the flight (timings[3] / [4]): before and after the
@@ -567,14 +586,19 @@ struct orcg_reader {
   int open_tail();
   // (sel: the column selection of the read it prepares for; prepare reads
   // nothing else the decodes change, so it runs without mu)
-  int prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel, const std::string& local_zone) const;
-  int prepare(uint64_t s, HostStage& hs) const { return prepare(s, hs, selected, local_tz); }
+  int prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel, const std::string& local_zone,
+              bool device_inflate) const;
+  int prepare(uint64_t s, HostStage& hs) const { return prepare(s, hs, selected, local_tz, dev_inflate); }
+  // whether the stripe's stream (col, slot) is one the host never walks: raw
+  // bytes or varints, which a Snappy file's chunks can inflate on the device
+  bool host_never_walks(const HostStage& hs, uint32_t col, int slot) const;
   // prepare()'s phases (reader_prepare.cpp). A stream the stripe reads:
   struct Need {
     uint32_t col;
     int slot;
     std::vector<Chunk> chunks;
     uint64_t file_off = 0;  // stream start in the file
+    bool device = false;    // inflated on the device: staging takes its compressed chunks
   };
   int locate_streams(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel, const std::string& local_zone,
                      StripeFooter& sf, std::vector<int>& row_index, std::vector<Need>& needs) const;

@@ -187,19 +187,29 @@ int orcg_reader::load_streams(HostStage& hs, std::vector<Need>& needs, double* t
     hs.t_io = now_s() - ti;
     hs.n_io = needs.size() + 1;  // + the stripe footer
   }
-  // staging: every chunk gets a slot of its maximum size, compacted after
-  uint64_t at = 0;
+  // staging: every chunk the host inflates gets a slot of its maximum size,
+  // compacted after; a device-inflated stream's chunks are copied compressed
+  // behind the compacted streams, with room for the stripe's chunk table
+  uint64_t at = 0, comp_bytes = 0, dev_chunks = 0;
   std::vector<std::pair<size_t, size_t>> all;
   for (size_t i = 0; i < needs.size(); ++i) {
-    at = (at + 255) & ~(uint64_t)255;
+    if (!needs[i].device) at = (at + 255) & ~(uint64_t)255;
     for (size_t j = 0; j < needs[i].chunks.size(); ++j) {
       Chunk& ch = needs[i].chunks[j];
-      ch.dst_off = at;
-      at += ch.original ? ch.src_len : ps.block_size;
+      if (needs[i].device) {
+        comp_bytes += ch.src_len;
+        ++dev_chunks;
+      } else {
+        ch.dst_off = at;
+        at += ch.original ? ch.src_len : ps.block_size;
+      }
       all.emplace_back(i, j);
     }
+    if (needs[i].device) comp_bytes = (comp_bytes + 255) & ~(uint64_t)255;
   }
-  if (!hs.ensure(at + 64, 0)) return hs.fail(ORCG_OUT_OF_MEMORY, "pinned staging allocation failed");
+  const uint64_t table_bytes = (dev_chunks * sizeof(orcg_snappy_chunk) + 255) & ~(uint64_t)255;
+  if (!hs.ensure(at + 256 + comp_bytes + table_bytes + 64, 0))
+    return hs.fail(ORCG_OUT_OF_MEMORY, "pinned staging allocation failed");
   *t_inflate = now_s();
   std::vector<std::string> errs(all.size());
   std::atomic<bool> bad{false};
@@ -208,7 +218,19 @@ int orcg_reader::load_streams(HostStage& hs, std::vector<Need>& needs, double* t
     for (auto& ch : nd.chunks) src_bytes += ch.src_len;
   // ~64 KB of compressed input per thread (stored chunks are copies: more)
   parallel_for(all.size(), [&](size_t q) {
+    const Need& nd = needs[all[q].first];
     Chunk& ch = needs[all[q].first].chunks[all[q].second];
+    if (nd.device) {
+      // the preamble alone: the chunk's length without inflating it
+      const PlanChunk pc{ch.src_off, ch.src_len, ch.original};
+      std::vector<orcg_snappy_chunk> one;
+      const char* e = "";
+      if (!plan_snappy_chunks(file, file_len, &pc, 1, ps.block_size, 0, one, &ch.dst_len, &e)) {
+        errs[q] = e;
+        bad = true;
+      }
+      return;
+    }
     const uint64_t cap = ch.original ? ch.src_len : ps.block_size;
     if (!decompress_chunk(ps.compression, file, ch, hs.h + ch.dst_off, cap, errs[q])) bad = true;
   }, src_bytes, ps.compression == kNone ? (1u << 20) : (64u << 10));
@@ -217,6 +239,7 @@ int orcg_reader::load_streams(HostStage& hs, std::vector<Need>& needs, double* t
       if (!e.empty()) return hs.fail(ORCG_PARSE_ERROR, e);
   uint64_t w = 0;  // compact (destinations never pass their sources)
   for (size_t i = 0; i < needs.size(); ++i) {
+    if (needs[i].device) continue;
     w = (w + 255) & ~(uint64_t)255;
     const uint64_t s0 = w;
     for (auto& ch : needs[i].chunks) {
@@ -227,6 +250,32 @@ int orcg_reader::load_streams(HostStage& hs, std::vector<Need>& needs, double* t
     sb.present = true;
     sb.host_off = s0;
     sb.len = w - s0;
+  }
+  // the device-inflated streams: compressed chunks into staging, their
+  // decompressed bytes laid out in the tail (offsets relative to it until
+  // prepare() places the tail)
+  uint64_t tail = 0;
+  for (size_t i = 0; i < needs.size(); ++i) {
+    if (!needs[i].device) continue;
+    w = (w + 255) & ~(uint64_t)255;
+    tail = (tail + 255) & ~(uint64_t)255;
+    StreamBuf& sb = hs.cols[needs[i].col].s[needs[i].slot];
+    sb.present = true;
+    sb.device_only = true;
+    sb.host_off = tail;
+    for (auto& ch : needs[i].chunks) {
+      if (ch.src_len) memcpy(hs.h + w, file + ch.src_off, ch.src_len);
+      hs.inflate.push_back({w, ch.src_len, tail, ch.dst_len, ch.original ? (uint64_t)ORCG_SNAPPY_STORED : 0});
+      w += ch.src_len;
+      tail += ch.dst_len;
+    }
+    sb.len = tail - sb.host_off;
+  }
+  if (!hs.inflate.empty()) {
+    w = (w + 255) & ~(uint64_t)255;
+    hs.inflate_off = w;
+    w += hs.inflate.size() * sizeof(orcg_snappy_chunk);
+    hs.tail_bytes = tail;
   }
   hs.n_chunks = all.size();
   *used = w;
@@ -481,9 +530,19 @@ int orcg_reader::layout_staging(uint64_t s, HostStage& hs, const std::vector<Str
 // (Compression.cc) in parallel chunks, run plans + segment tables.
 // (Small streams on host plans instead of row-index segment tables were
 // measured in round 4, profiles/r04/*small_stream_ab*: no gain, dropped.)
+bool orcg_reader::host_never_walks(const HostStage& hs, uint32_t col, int slot) const {
+  if (slot == kSlotDict) return true;
+  if (slot != kSlotData) return false;
+  const StreamLayout lay = stream_layout(footer.types[col], hs.cols[col].encoding, decimal_as_long, false);
+  const StreamDesc* d = lay.find(slot);
+  return d && (d->coding == kRaw || d->coding == kVarint);
+}
+
 int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& selected,
-                         const std::string& local_zone) const {
+                         const std::string& local_zone, bool device_inflate) const {
   hs.stripe = s;
+  hs.inflate.clear();
+  hs.inflate_off = hs.tail_off = hs.tail_bytes = 0;
   hs.rc = ORCG_OK;
   hs.err.clear();
   const double t0 = now_s();
@@ -492,6 +551,10 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
   std::vector<Need> needs;
   int rc = locate_streams(s, hs, selected, local_zone, sf, row_index, needs);
   if (rc) return rc;
+  // Snappy chunks of the streams the host never walks inflate on the device
+  // (a block size past the kernel's 32-bit offsets keeps the host path)
+  if (device_inflate && ps.compression == kSnappy && ps.block_size < kSnappyMaxBytes)
+    for (Need& nd : needs) nd.device = host_never_walks(hs, nd.col, nd.slot);
   double t1 = 0;
   uint64_t w = 0;
   if ((rc = load_streams(hs, needs, &t1, &w))) return rc;
@@ -500,6 +563,15 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
   std::vector<StreamBuf*> rle;
   build_plans(selected, hs, rle);
   if ((rc = layout_staging(s, hs, rle, w))) return rc;
+  if (!hs.inflate.empty()) {
+    // the tail: past everything issue() uploads (used + slack bounds it)
+    hs.tail_off = (hs.used + hs.slack + 255) & ~(uint64_t)255;
+    for (Col& c : hs.cols)
+      for (StreamBuf& sb : c.s)
+        if (sb.device_only) sb.host_off += hs.tail_off;
+    for (orcg_snappy_chunk& k : hs.inflate) k.dst_offset += hs.tail_off;
+    memcpy(hs.h + hs.inflate_off, hs.inflate.data(), hs.inflate.size() * sizeof(orcg_snappy_chunk));
+  }
   const double t2 = now_s();
   hs.t_parse = t1 - t0;
   hs.t_decomp = t15 - t1;

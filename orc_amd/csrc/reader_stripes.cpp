@@ -87,6 +87,13 @@ int orcg_reader::first_error(int inline_rc) {
   std::stable_sort(F->checks.begin(), F->checks.end(),
                    [](const std::pair<uint32_t, std::function<int()>>& a,
                       const std::pair<uint32_t, std::function<int()>>& b) { return a.first < b.first; });
+  // a chunk the device could not inflate: ahead of any column's error (the
+  // host's inflate fails the stripe in prepare(), before any column decodes)
+  if (F->inflate_word && F->h_rb[F->inflate_word] != kNoError) {
+    const unsigned long long r = F->h_rb[F->inflate_word];
+    ctx->last_error_value = r >> 8;
+    return fail(dev_error_status((uint32_t)(r & 0xff)), dev_error_message((uint32_t)(r & 0xff)));
+  }
   size_t ci = 0;
   for (uint32_t col = 0; col < nc && col <= last; ++col) {
     for (; ci < F->checks.size() && F->checks[ci].first <= col; ++ci) {
@@ -156,7 +163,7 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   {
     size_t nsel = 0;
     for (size_t i = 0; i < hs.cols.size(); ++i) nsel += selected[i] && hs.cols[i].supported ? 1 : 0;
-    ds.pool.hint = hs.used + hs.slack + 16 * nsel * footer.stripes[hs.stripe].num_rows + (1u << 20);
+    ds.pool.hint = hs.used + hs.slack + hs.tail_bytes + 256 + 16 * nsel * footer.stripes[hs.stripe].num_rows + (1u << 20);
   }
   const size_t nc = hs.cols.size();
   const uint64_t nrows_stripe = footer.stripes[hs.stripe].num_rows;
@@ -167,14 +174,19 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   const uint64_t rb_off = (hs.used + 255) & ~(uint64_t)255;
   fl.rb_words = rb_words_for(nc);
   fl.rb_used = 2 * nc + 1;  // word 2 nc: the context's own record during this stripe
+  // then the device inflate's record ((chunk index << 8) | code)
+  fl.inflate_word = hs.inflate.empty() ? 0 : fl.rb_used++;
   const uint64_t arena_off = (rb_off + 8 * fl.rb_words + 255) & ~(uint64_t)255;
   const uint64_t arena_cap = arena_bytes_for(nc, v1_segments(hs), (nrows_stripe + 2047) / 2048 + 1);
   const uint64_t total = arena_off + arena_cap;
+  // the device-only tail (streams the device inflates) lies past the upload
+  if (!hs.inflate.empty() && total + 64 > hs.tail_off)
+    return early(fail(ORCG_DEVICE_ERROR, "stripe upload overlaps its device-inflated streams"));
   if (!hs.ensure(total + 64, hs.used)) return early(fail(ORCG_OUT_OF_MEMORY, "pinned staging allocation failed"));
   memset(hs.h + rb_off, 0xff, 8 * nc);
   memset(hs.h + rb_off + 8 * nc, 0, 8 * (fl.rb_words - nc));
-  memset(hs.h + rb_off + 8 * (2 * nc), 0xff, 8);
-  ds.d_stage = (uint8_t*)ds.pool.get(total + 64);
+  memset(hs.h + rb_off + 8 * (2 * nc), 0xff, 8 * (fl.inflate_word ? 2 : 1));
+  ds.d_stage = (uint8_t*)ds.pool.get(std::max(total, hs.tail_off + hs.tail_bytes) + 64);
   if (!ds.d_stage) return early(fail_oom(__FILE_NAME__, __LINE__));
   ds.d_rb = (uint64_t*)(ds.d_stage + rb_off);
   ds.d_errs = (unsigned long long*)ds.d_rb;
@@ -280,6 +292,16 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   if (urc && !rc) rc = fail_ctx(urc);
   if (fl.ev_split && hipEventRecord(fl.ev_up1, ctx->stream) != hipSuccess) fl.ev_split = false;
   fl.t1 = now_s();
+  // the stripe's Snappy chunks, ahead of every decode: compressed bytes and
+  // the chunk table rode the upload, the streams land in the tail
+  if (!rc && !hs.inflate.empty()) {
+    if ((rc = launch_snappy_inflate(ctx, ds.d_stage, (const orcg_snappy_chunk*)(ds.d_stage + hs.inflate_off),
+                                    hs.inflate.size(), ds.d_stage,
+                                    (unsigned long long*)(ds.d_rb + fl.inflate_word))))
+      rc = fail_ctx(rc);
+    last_dev_inflate[0] += hs.inflate.size();
+    for (const orcg_snappy_chunk& k : hs.inflate) last_dev_inflate[1] += k.dst_bytes;
+  }
   // A batch of nested or nullable columns' dictionaries only (collect_dicts;
   // configs[4]'s map keys): nothing reads its offsets before the fork's next
   // level, so it runs on side lane 0 beside the stripe's first decodes, not
@@ -396,6 +418,7 @@ int orcg_reader::read_stripes(uint64_t first, uint64_t count) {
   stream_stats[0] = stream_stats[1] = 0;
   batched_streams = 0;
   stage_bytes = 0;
+  last_dev_inflate[0] = last_dev_inflate[1] = 0;
   while (slots.size() < count) slots.emplace_back(new DevSlot());
   nslots = 0;
   if (count == 0) return ORCG_OK;

@@ -89,6 +89,7 @@ struct orcg_row_reader {
   std::string local_tz;                  // the zone of stripes that name none
   std::shared_ptr<const ReadPlan> read;  // setReadType: the reader's at creation
   bool evo_throw = false;                // throwOnSchemaEvolutionOverflow, likewise
+  bool dev_inflate = false;              // orcg_reader_set_device_decompression, likewise
   uint64_t nstripes = 0, first = 0, last = 0;  // stripes [first, last) are in range
   uint64_t current = 0, row_in_stripe = 0, rows_in_stripe = 0;
   uint64_t previous_row = 0;
@@ -247,7 +248,7 @@ struct orcg_row_reader {
         prepared[u & 1] = u;
         ahead = std::thread([this, u] {
           const double tp = now_s();
-          (void)r->prepare(u, stage[u & 1], selected, local_tz);  // a failure is kept in the stage
+          (void)r->prepare(u, stage[u & 1], selected, local_tz, dev_inflate);  // a failure is kept in the stage
           addp(4, now_s() - tp);
         });
       }
@@ -255,7 +256,7 @@ struct orcg_row_reader {
     if (prepared[t & 1] == t) start_ahead();
     {
       std::lock_guard<std::mutex> lk(r->mu);
-      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz, read, evo_throw);
+      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz, read, evo_throw, dev_inflate);
       (void)hipSetDevice(r->ctx->device);
       rc = ORCG_OK;
       if (prepared[t & 1] != t) {
@@ -396,6 +397,7 @@ int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* o, orc
     // and of its read type and overflow rule
     rr->read = r->own_read;
     rr->evo_throw = r->own_evo_throw;
+    rr->dev_inflate = r->own_dev_inflate;
   }
   if (o && o->timezone) {
     const ZoneEntry* z = r->resolve_zone(o->timezone);

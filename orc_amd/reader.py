@@ -485,6 +485,19 @@ class Reader:
         """RowReaderOptions::setEnableLazyDecoding for stripe reads."""
         check(self._L.orcg_reader_set_lazy_dictionary(self._h, int(bool(on))), self._err)
 
+    def set_device_decompression(self, on=True):
+        """Inflate a Snappy file's chunks of raw byte streams (direct string /
+        binary DATA, DICTIONARY_DATA, float / double DATA, varint decimal
+        DATA) on the device instead of the host. Off by default; other codecs
+        ignore it. Row readers created afterwards take it with them."""
+        check(self._L.orcg_reader_set_device_decompression(self._h, int(bool(on))), self._err)
+
+    def last_device_inflate(self):
+        """(chunks, decompressed bytes) the last read inflated on the device."""
+        out = (ctypes.c_uint64 * 2)()
+        check(self._L.orcg_reader_last_device_inflate(self._h, out), self._err)
+        return int(out[0]), int(out[1])
+
     def create_row_reader(self, include=None, offset=0, length=None, lazy_dictionary=False, tight_numeric=False,
                           timezone=None, read_type=_KEEP, throw_on_overflow=_KEEP):
         """Reader::createRowReader(RowReaderOptions): `include` type ids (or
