@@ -589,8 +589,8 @@ int export_stripe(orcg_reader* r, int dictionary, bool host, ArrowArray* out) {
   if (!r || !out) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
   memset(out, 0, sizeof *out);
-  Export e{r, r->own_ctx, nullptr, dictionary != 0, r->own_sel};
-  if (!r->own_ctx) return e.fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
+  Export e{r, r->own.ctx, nullptr, dictionary != 0, r->own.selected};
+  if (!r->own.ctx) return e.fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (r->nslots == 0 || r->slots.empty()) return e.fail(ORCG_INVALID_ARGUMENT, "no decoded stripe to export");
   e.slot = r->slots[0].get();
   return e.run(host, out);
@@ -609,8 +609,8 @@ int orcg_reader_arrow_schema(const orcg_reader* r, int dictionary, struct ArrowS
   const DevSlot* slot = nullptr;
   {
     std::lock_guard<std::mutex> lk(rw->mu);
-    sel = r->own_sel;
-    plan = r->own_read;
+    sel = r->own.selected;
+    plan = r->own.read;
     if (dictionary && r->nslots > 0 && !r->slots.empty()) slot = r->slots[0].get();
   }
   if (r->footer.types.empty() || r->footer.types[0].kind != ORCG_TYPE_STRUCT)
@@ -629,7 +629,7 @@ int orcg_reader_export_arrow_device(orcg_reader* r, int dictionary, struct Arrow
   memset(out, 0, sizeof *out);
   const int rc = export_stripe(r, dictionary, false, &out->array);
   if (rc) return rc;
-  out->device_id = r->own_ctx->device;
+  out->device_id = r->own.ctx->device;
   out->device_type = ARROW_DEVICE_ROCM;
   out->sync_event = nullptr;  // the stream was synchronised
   return ORCG_OK;

@@ -761,7 +761,7 @@ int plan_dict_multi(Ctx* ctx, const DictJob* jobs, uint32_t njobs, std::vector<M
   const void* d = nullptr;
   const int rc = stage_table(ctx, g.data(), g.size() * sizeof(DictJob), &d);
   if (rc) return rc;
-  out.push_back(MultiLaunch{2, 0, d, (uint32_t)g.size(), g.size(), 0});
+  out.push_back(MultiLaunch{MultiLaunch::kDict, 0, d, (uint32_t)g.size(), g.size(), 0});
   return ORCG_OK;
 }
 

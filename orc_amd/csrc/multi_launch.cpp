@@ -49,9 +49,9 @@ int stage_table(Ctx* ctx, const void* src, size_t bytes, const void** out) {
 // The planned launches, in order. The work before the join runs side by
 // side: the critical RLEv2 instance (the two-pass one, else the one with the
 // most values) on this stream, every other instance on a side lane of its
-// own, and the varint tile counts and RLEv1 segments (kinds 4, 1) on one
+// own, and the varint tile counts and RLEv1 segments (on_aux_lane) on one
 // more lane; then this stream waits for the lanes and runs what reads their
-// outputs (dictionaries, decimals, length scans: kinds 2, 5, 6) itself. The
+// outputs (dictionaries, decimals, length scans: joins_first) itself. The
 // critical path never changes queues: a dependency across HIP queues costs
 // 12-30 us a hop on the MI355X (configs[3] timelines), so the lanes, done
 // long before the critical instance, are the ones waited on, and the
@@ -61,8 +61,8 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
   bool aux = false;
   for (size_t i = 0; i < ls.size(); ++i) {
     const MultiLaunch& m = ls[i];
-    if (m.kind == 1 || m.kind == 4) aux = true;
-    if (m.kind != 0) continue;
+    if (on_aux_lane(m.kind)) aux = true;
+    if (m.kind != MultiLaunch::kRlev2) continue;
     ++ninst;
     const bool two = m.spg > 0, ctwo = crit >= 0 && ls[crit].spg > 0;
     if (crit < 0 || (two && !ctwo) || (two == ctwo && m.values > ls[crit].values)) crit = (int)i;
@@ -90,9 +90,9 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
   };
   for (size_t i = 0; i < ls.size() && !rc; ++i) {
     const MultiLaunch& m = ls[i];
-    if ((m.kind == 2 || m.kind == 5 || m.kind == 6) && !joined && (rc = join())) break;
+    if (joins_first(m.kind) && !joined && (rc = join())) break;
     debug_stale("run_multi: before a launch");
-    if (m.kind == 0) {
+    if (m.kind == MultiLaunch::kRlev2) {
       Ctx* c = base;
       if (par && (int)i != crit && (rc = fork(&c))) break;
       // jobs without a record of their own report into the base's (the
@@ -107,7 +107,7 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
                  (unsigned long long)m.grid, c == base ? "" : ", side lane");
         base->last_error = c->last_error + b;
       }
-    } else if (m.kind == 1 || m.kind == 4) {
+    } else if (on_aux_lane(m.kind)) {
       Ctx* c = base;
       if (par && !joined) {
         if (aux_lane < 0) {
@@ -118,7 +118,7 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
       }
       unsigned long long* const own = c->d_err;
       c->d_err = base->d_err;
-      if (m.kind == 1) {
+      if (m.kind == MultiLaunch::kRlev1) {
         rc = launch_rlev1_jobs(c, (const V1SegDesc*)m.d_jobs, m.grid, m.variant);
       } else {
         const VarintJob& J = *(const VarintJob*)m.d_jobs;
@@ -128,15 +128,15 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
       }
       c->d_err = own;
       if (rc && c != base) base->last_error = c->last_error;
-    } else if (m.kind == 2) {
+    } else if (m.kind == MultiLaunch::kDict) {
       rc = launch_dict_jobs(base, (const DictJob*)m.d_jobs, m.njobs, m.grid);
-    } else if (m.kind == 5) {
+    } else if (m.kind == MultiLaunch::kDecimal) {
       rc = launch_decimal_jobs(base, (const DecJob*)m.d_jobs, m.njobs, m.grid, m.variant);
-    } else if (m.kind == 6) {
+    } else if (m.kind == MultiLaunch::kLengthScan) {
       const ScanJob& J = *(const ScanJob*)m.d_jobs;
       rc = launch_exclusive_scan(base, J.in, J.n, J.out, J.flags, J.total);
     } else {
-      // a pinned single-stream variant: host job (d_jobs is a host pointer)
+      // kRlev2Pinned, a pinned single-stream variant: host job (d_jobs is a host pointer)
       const RleJob& J = *(const RleJob*)m.d_jobs;
       unsigned long long* const saved = base->d_err;  // the job's own error record
       if (J.err) base->d_err = J.err;

@@ -226,22 +226,36 @@ inline int stage_rle_jobs(Ctx* ctx, const RleJob* jobs, uint32_t n, const RleJob
 // table (stage_table in arena mode): plan_* group, order and stage the
 // jobs; run_multi enqueues the kernels (RLEv2 instances on side lanes).
 struct MultiLaunch {
-  int kind;           // 0 RLEv2 instance `variant`, 1 RLEv1, 2 dictionaries, 3 pinned single-stream RLEv2
-                      // (host job), 4 varint tile counts + scan (host VarintJob), 5 decimal columns (DecJob
-                      // table, `variant` = the decimal mode), 6 a direct string column's length scan (host
-                      // ScanJob)
+  enum Kind : int {
+    kRlev2,         // RLEv2 instance `variant`
+    kRlev1,         // RLEv1 segments, `variant` = the chunk width
+    kDict,          // dictionaries
+    kRlev2Pinned,   // pinned single-stream RLEv2 (host job)
+    kVarintCounts,  // varint tile counts + scan (host VarintJob)
+    kDecimal,       // decimal columns (DecJob table, `variant` = the decimal mode)
+    kLengthScan,    // a direct string column's length scan (host ScanJob)
+  };
+  Kind kind;
   int variant;
   const void* d_jobs;
   uint32_t njobs;
   uint64_t grid;      // segments / tiles
   uint64_t values;
-  // two-pass RLEv2 launch (kind 0, spg > 0): run-table entries, slices per
+  // two-pass RLEv2 launch (kRlev2, spg > 0): run-table entries, slices per
   // segment and values per slice (RunTab)
   uint64_t tab_entries = 0;
   uint32_t spg = 0, slice = 0;
 };
+// The scheduler's rule (run_multi): the RLEv2 instances run side by side
+// from the fork; these need only stream bytes and share one auxiliary lane
+// before the join ...
+inline bool on_aux_lane(MultiLaunch::Kind k) { return k == MultiLaunch::kRlev1 || k == MultiLaunch::kVarintCounts; }
+// ... and these read the lanes' outputs, so the join comes first
+inline bool joins_first(MultiLaunch::Kind k) {
+  return k == MultiLaunch::kDict || k == MultiLaunch::kDecimal || k == MultiLaunch::kLengthScan;
+}
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out);
-// One planned RLEv2 launch (kind 0) over its staged job table, on ctx's stream:
+// One planned RLEv2 launch (kRlev2) over its staged job table, on ctx's stream:
 // run_multi's entry into the tiled instances (rlev2_tiled.hip).
 int launch_rlev2_tiled_jobs(Ctx* ctx, const MultiLaunch& m);
 // A varint DATA stream's tile counts and their scan (the first value of each

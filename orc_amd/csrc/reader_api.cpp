@@ -10,7 +10,7 @@
 static thread_local std::string t_open_error;
 
 orcg_reader::~orcg_reader() {
-  if (ev_pre) (void)hipEventDestroy(ev_pre);
+  if (B.ev_pre) (void)hipEventDestroy(B.ev_pre);
   if (h_pub) (void)hipHostFree(h_pub);
   slots.clear();
   if (mapped) munmap(mapped, file_len);
@@ -78,7 +78,7 @@ int orcg_reader_open(orcg_ctx* ctx, const uint8_t* file, uint64_t file_len, orcg
   if (!out || (file_len && !file)) return ORCG_INVALID_ARGUMENT;
   *out = nullptr;
   std::unique_ptr<orcg_reader> r(new orcg_reader());
-  r->own_ctx = ctx;
+  r->own.ctx = ctx;
   r->file = file;
   r->file_len = file_len;
   const int rc = r->open_tail();
@@ -111,7 +111,7 @@ int orcg_reader_open_file(orcg_ctx* ctx, const char* path, orcg_reader** out) {
     return ORCG_INVALID_ARGUMENT;
   }
   std::unique_ptr<orcg_reader> r(new orcg_reader());
-  r->own_ctx = ctx;
+  r->own.ctx = ctx;
   r->file = (const uint8_t*)m;
   r->file_len = len;
   r->mapped = m;
@@ -155,13 +155,13 @@ const uint8_t* orcg_reader_metadata_value(const orcg_reader* r, uint32_t i, uint
 int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_lazy = on != 0;
+  r->own.lazy_dict = on != 0;
   return ORCG_OK;
 }
 int orcg_reader_set_device_decompression(orcg_reader* r, int on) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_dev_inflate = on != 0;
+  r->own.dev_inflate = on != 0;
   return ORCG_OK;
 }
 int orcg_reader_last_device_inflate(const orcg_reader* r, uint64_t out2[2]) {
@@ -191,20 +191,20 @@ int orcg_reader_set_read_type(orcg_reader* r, const char* type_string) {
       return r->fail_user(ORCG_INVALID_ARGUMENT, err);
   }
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_read = plan;
+  r->own.read = plan;
   return ORCG_OK;
 }
 
 int orcg_reader_set_throw_on_schema_evolution_overflow(orcg_reader* r, int on) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_evo_throw = on != 0;
+  r->own.evo_throw = on != 0;
   return ORCG_OK;
 }
 
 int orcg_reader_read_type(const orcg_reader* r, uint32_t id, orcg_type_info* out) {
   if (!r || !out || id >= r->footer.types.size()) return ORCG_INVALID_ARGUMENT;
-  const std::shared_ptr<const ReadPlan> plan = r->own_read;
+  const std::shared_ptr<const ReadPlan> plan = r->own.read;
   if (!plan || plan->conv[id] != rt::kConvert) return orcg_reader_type(r, id, out);
   const rt::Node& n = plan->tree[id];
   out->kind = n.kind;
@@ -256,14 +256,14 @@ int orcg_reader_set_timezone_name(orcg_reader* r, const char* name) {
   if (!z) return r->fail_user(ORCG_INVALID_ARGUMENT, std::string("Time zone ") + name + " not found");
   if (!z->zone) return r->fail_user(ORCG_PARSE_ERROR, z->err);
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_reader_tz = z;
+  r->own.reader_tz = z;
   return ORCG_OK;
 }
 
 int orcg_reader_set_local_timezone(orcg_reader* r, const char* name) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_local_tz = name ? name : "";
+  r->own.local_tz = name ? name : "";
   return ORCG_OK;
 }
 int orcg_reader_format_version(const orcg_reader* r, uint32_t* major, uint32_t* minor) {
@@ -311,32 +311,30 @@ int orcg_reader_select(orcg_reader* r, const uint8_t* include, uint32_t ntypes) 
   const int rc = compute_selection(r, include, ntypes, sel);
   if (rc) return rc;
   std::lock_guard<std::mutex> lk(r->mu);
-  r->own_sel.swap(sel);
+  r->own.selected.swap(sel);
   return ORCG_OK;
 }
 
 int orcg_reader_is_selected(const orcg_reader* r, uint32_t type_id) {
-  return r && type_id < r->own_sel.size() && r->own_sel[type_id] ? 1 : 0;
+  return r && type_id < r->own.selected.size() && r->own.selected[type_id] ? 1 : 0;
 }
 
 int orcg_reader_read_stripe(orcg_reader* r, uint64_t stripe) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw, r->own_dev_inflate);
+  orcg_reader::Active scope(r, r->own);
   return r->read_stripes(stripe, 1);
 }
 
 int orcg_reader_bench_stripe_decode(orcg_reader* r, uint64_t stripe, uint32_t iters, double* decode_s, double* h2d_s) {
   if (!r || !decode_s || !h2d_s || iters == 0) return ORCG_INVALID_ARGUMENT;
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw, r->own_dev_inflate);
-  if (!r->ctx) return r->fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
+  orcg_reader::Active scope(r, r->own);
+  if (!r->act.ctx) return r->fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (stripe >= r->footer.stripes.size()) return r->fail(ORCG_INVALID_ARGUMENT, "stripe index out of range");
-  hipSetDevice(r->ctx->device);
-  int rc = r->prepare(stripe, r->stages[0]);
+  hipSetDevice(r->act.ctx->device);
+  int rc = r->prepare(stripe, r->stages[0], r->act);
   if (rc) return rc;
   if (r->slots.empty()) r->slots.emplace_back(new DevSlot());
   // one untimed decode (allocations), then `iters` back-to-back decodes of
@@ -354,8 +352,7 @@ int orcg_reader_read_stripes(orcg_reader* r, uint64_t first, uint64_t count) {
   if (!r) return ORCG_INVALID_ARGUMENT;
   ReaderCallScope call(r);
   std::lock_guard<std::mutex> lk(r->mu);
-  orcg_reader::Active act(r, r->own_ctx, r->own_sel, r->own_lazy, r->own_reader_tz, r->own_local_tz, r->own_read,
-                          r->own_evo_throw, r->own_dev_inflate);
+  orcg_reader::Active scope(r, r->own);
   return r->read_stripes(first, count);
 }
 
@@ -374,9 +371,9 @@ int orcg_reader_column(const orcg_reader* r, uint32_t id, orcg_column_view* out)
 }
 
 int orcg_reader_copy_to_host(orcg_reader* r, void* dst, const void* src, uint64_t bytes) {
-  if (!r || !r->own_ctx || (bytes && (!dst || !src))) return ORCG_INVALID_ARGUMENT;
+  if (!r || !r->own.ctx || (bytes && (!dst || !src))) return ORCG_INVALID_ARGUMENT;
   if (!bytes) return ORCG_OK;
-  Ctx* c = r->own_ctx;  // never a row reader worker's context
+  Ctx* c = r->own.ctx;  // never a row reader worker's context
   int rc = hip_check(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream), "D2H");
   if (!rc) rc = sync_ctx(c);
   return rc;

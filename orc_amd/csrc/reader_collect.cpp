@@ -14,7 +14,7 @@ int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t coun
   const bool v1 = rle_v1(c.encoding, desc.force_v2);
   if (!sb.pos && count > sb.plan->values) return ORCG_OK;
   // (collect() runs before the stripe's upload: no device work here)
-  if (sb.pos && !(cur_rows && (v1 || rlev2_multi_capable(ctx->rlev2_variant)))) return ORCG_OK;
+  if (sb.pos && !(cur_rows && (v1 || rlev2_multi_capable(act.ctx->rlev2_variant)))) return ORCG_OK;
   if (v1) {
     // RLEv1: one host-built descriptor per segment (the plan's cuts, or the
     // row index with the stripe's row-group starts g * stride)
@@ -44,10 +44,10 @@ int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t coun
       d.nvalues = count;
       d.err = D->d_errs + id;
       d.is_signed = is_signed ? 1u : 0u;
-      v1_segs.push_back(d);
+      B.v1_segs.push_back(d);
     }
     madd(kMDecodeCall, 1);
-    batched[(uint64_t)id * 8 + (uint64_t)slot] = {out, count};
+    B.put(id, slot, out, count);
     return ORCG_OK;
   }
   RleJob j{};
@@ -73,9 +73,9 @@ int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t coun
   j.nvalues = count;
   j.is_signed = is_signed ? 1u : 0u;
   j.err = D->d_errs + id;
-  batch.push_back(j);
+  B.rlev2.push_back(j);
   madd(kMDecodeCall, 1);
-  batched[(uint64_t)id * 8 + (uint64_t)slot] = {out, count};
+  B.put(id, slot, out, count);
   return ORCG_OK;
 }
 
@@ -87,26 +87,31 @@ int orcg_reader::queue_dict(uint32_t id, uint64_t n) {
   const uint64_t D_ = c.dict_size;
   if (D_ > kDictLds || !c.s[kSlotData].present) return ORCG_OK;
   if (D_ > 0 && !c.s[kSlotLength].present) return ORCG_OK;  // decode() raises the missing stream
-  const auto li = batched.find((uint64_t)id * 8 + kSlotLength);
-  const auto di = batched.find((uint64_t)id * 8 + kSlotData);
-  if ((D_ > 0 && li == batched.end()) || (n > 0 && di == batched.end())) return ORCG_OK;
+  const StripeBatch::Values* li = B.find(id, kSlotLength);
+  const StripeBatch::Values* di = B.find(id, kSlotData);
+  if ((D_ > 0 && !li) || (n > 0 && !di)) return ORCG_OK;
+  return push_dict(id, D_ ? li->values : nullptr, n ? di->values : nullptr, n, !act.lazy_dict, B.dict_done);
+}
+
+int orcg_reader::push_dict(uint32_t id, const int64_t* lengths, const int64_t* idx, uint64_t n, bool gather,
+                           std::unordered_map<uint32_t, StripeBatch::DictDone>& done) {
   DictJob j{};
-  j.lengths = D_ ? li->second.first : nullptr;
-  j.dict_size = D_;
-  ORCG_ALLOC_TO(int64_t, j.offsets, D_ + 1);
+  j.lengths = lengths;
+  j.dict_size = H->cols[id].dict_size;
+  ORCG_ALLOC_TO(int64_t, j.offsets, j.dict_size + 1);
   const uint64_t* h_summary = nullptr;
   j.summary = rb_alloc(2, &h_summary);
-  if (!j.summary) return ORCG_OK;
-  j.idx = n ? di->second.first : nullptr;
+  if (!j.summary) return ORCG_OK;  // no read-back slots: decode() does the dictionary itself
+  j.idx = idx;
   j.nn = nullptr;
-  j.n = lazy_dict ? 0 : n;
-  if (!lazy_dict) {
+  j.n = gather ? n : 0;  // 0: offsets and summary only (decode() gathers the rows, or decoding is lazy)
+  if (gather) {
     ORCG_ALLOC_TO(int64_t, j.start, n);
     ORCG_ALLOC_TO(int64_t, j.len, n);
   }
   j.err = D->d_errs + id;
-  dict_batch.push_back(j);
-  dict_done[id] = DictDone{j.offsets, h_summary, j.start, j.len, const_cast<int64_t*>(j.idx)};
+  B.dict_jobs.push_back(j);
+  done[id] = StripeBatch::DictDone{j.offsets, h_summary, j.start, j.len, const_cast<int64_t*>(j.idx)};
   return ORCG_OK;
 }
 
@@ -122,18 +127,18 @@ int orcg_reader::queue_varint(uint32_t id) {
   const uint64_t* h_total = nullptr;
   j.total = rb_alloc(1, &h_total);
   if (!j.total) return ORCG_OK;  // no read-back slot: decode() counts it itself
-  varint_jobs.push_back(j);
-  varint_pre[id] = {j.base, h_total};
-  launches.push_back(MultiLaunch{4, 0, &varint_jobs.back(), 1, 0, 0});
+  B.varint_jobs.push_back(j);
+  B.varint_pre[id] = {j.base, h_total};
+  B.launches.push_back(MultiLaunch{MultiLaunch::kVarintCounts, 0, &B.varint_jobs.back(), 1, 0, 0});
   return ORCG_OK;
 }
 
 int orcg_reader::queue_decimal(uint32_t id, uint64_t n) {
   const file::TypeInfo& t = footer.types[id];
   if (t.precision == 0 || n == 0) return ORCG_OK;  // Hive 0.11: the per-column path (its checks, nulling)
-  const auto vp = varint_pre.find(id);
-  const auto sc = batched.find((uint64_t)id * 8 + (uint64_t)kSlotSecondary);
-  if (vp == varint_pre.end() || sc == batched.end() || sc->second.second != n) return ORCG_OK;
+  const auto vp = B.varint_pre.find(id);
+  const StripeBatch::Values* sc = B.find(id, kSlotSecondary);
+  if (vp == B.varint_pre.end() || !sc || sc->count != n) return ORCG_OK;
   const bool wide = t.precision > 18;
   Col& c = H->cols[id];
   const StreamBuf& sb = c.s[kSlotData];
@@ -141,31 +146,31 @@ int orcg_reader::queue_decimal(uint32_t id, uint64_t n) {
   j.src = D->d_stage + sb.host_off;
   j.len = sb.len;
   j.tile_base = vp->second.first;
-  j.scales = sc->second.first;
+  j.scales = sc->values;
   j.nvalues = n;
   j.err = D->d_errs + id;
   j.scale = (int32_t)t.scale;
   int64_t* out = nullptr;
   ORCG_ALLOC_TO(int64_t, out, wide ? 2 * n : n);
   j.out = out;
-  dec_batch[wide ? 1 : 0].push_back(j);
-  dec_done[id] = out;
+  B.dec_jobs[wide ? 1 : 0].push_back(j);
+  B.dec_done[id] = out;
   return ORCG_OK;
 }
 
 int orcg_reader::queue_scan(uint32_t id, uint64_t n) {
-  const auto li = batched.find((uint64_t)id * 8 + kSlotLength);
-  if (n == 0 || li == batched.end() || li->second.second != n || !H->cols[id].s[kSlotData].present) return ORCG_OK;
+  const StripeBatch::Values* li = B.find(id, kSlotLength);
+  if (n == 0 || !li || li->count != n || !H->cols[id].s[kSlotData].present) return ORCG_OK;
   ScanJob j{};
-  j.in = li->second.first;
+  j.in = li->values;
   j.n = n;
   ORCG_ALLOC_TO(int64_t, j.out, n + 1);
   const uint64_t *h_fl = nullptr, *h_need = nullptr;
   j.flags = rb_alloc(2, &h_fl);
   j.total = j.flags ? rb_alloc(1, &h_need) : nullptr;
   if (!j.total) return ORCG_OK;  // no read-back slots: decode() scans it itself
-  scan_jobs.push_back(j);
-  scan_done[id] = ScanDone{j.out, h_fl, h_need, n};
+  B.scan_jobs.push_back(j);
+  B.scan_done[id] = StripeBatch::ScanDone{j.out, h_fl, h_need, n};
   return ORCG_OK;
 }
 
@@ -179,27 +184,16 @@ int orcg_reader::queue_scan(uint32_t id, uint64_t n) {
 // reads it whole whatever the rows (DictionaryLoader.cc:43-97).
 int orcg_reader::collect_dicts(uint32_t id) {
   Col& c = H->cols[id];
-  if (!selected[id] || !c.supported) return ORCG_OK;
+  if (!act.selected[id] || !c.supported) return ORCG_OK;
   const uint32_t k = c.kind;
   if (is_string_kind(k) && is_dict(c.encoding)) {
     const uint64_t D_ = c.dict_size;
     if (D_ == 0 || D_ > kDictLds || !c.s[kSlotLength].present) return ORCG_OK;
     int rc = queue_stream(id, *layout(id, c).find(kSlotLength), D_);
     if (rc) return rc;
-    const auto li = batched.find((uint64_t)id * 8 + kSlotLength);
-    if (li == batched.end() || li->second.second != D_) return ORCG_OK;
-    DictJob j{};
-    j.lengths = li->second.first;
-    j.dict_size = D_;
-    ORCG_ALLOC_TO(int64_t, j.offsets, D_ + 1);
-    const uint64_t* h_summary = nullptr;
-    j.summary = rb_alloc(2, &h_summary);
-    if (!j.summary) return ORCG_OK;
-    j.n = 0;  // offsets and summary only: decode() gathers the rows
-    j.err = D->d_errs + id;
-    dict_batch.push_back(j);
-    dict_pre[id] = DictDone{j.offsets, h_summary, nullptr, nullptr, nullptr};
-    return ORCG_OK;
+    const StripeBatch::Values* li = B.find(id, kSlotLength);
+    if (!li || li->count != D_) return ORCG_OK;
+    return push_dict(id, li->values, nullptr, 0, false, B.dict_pre);
   }
   for (uint32_t st : footer.types[id].subtypes) {
     const int rc = collect_dicts(st);
@@ -214,7 +208,7 @@ int orcg_reader::collect_dicts(uint32_t id) {
 // slots and signedness from; then what the column's kind batches on top.
 int orcg_reader::collect(uint32_t id, uint64_t n, const int64_t* rg_rows) {
   Col& c = H->cols[id];
-  if (!selected[id] || !c.supported) return ORCG_OK;
+  if (!act.selected[id] || !c.supported) return ORCG_OK;
   if (c.s[kSlotPresent].present) return collect_dicts(id);  // its counts come from the device
   cur_rows = rg_rows;
   cur_n = n;
@@ -240,4 +234,32 @@ int orcg_reader::collect(uint32_t id, uint64_t n, const int64_t* rg_rows) {
       if ((rc = collect(st, n, rg_rows))) break;
   }
   return rc;
+}
+
+// The queued jobs as launches, their job tables staged into the arena. The
+// order the launches are appended in is the one run_multi assigns lanes by:
+// the varint counts (as queue_varint queued them), the RLEv2 instances,
+// RLEv1, the dictionaries, the decimals of mode 0 then 1, the length scans.
+int orcg_reader::plan_batch() {
+  Ctx* const ctx = act.ctx;
+  int rc = ORCG_OK;
+  if (!B.rlev2.empty()) rc = plan_rlev2_multi(ctx, B.rlev2.data(), (uint32_t)B.rlev2.size(), B.launches);
+  if (!rc && !B.v1_segs.empty()) rc = plan_rlev1_multi(ctx, B.v1_segs.data(), B.v1_segs.size(), B.launches);
+  if (!rc && !B.dict_jobs.empty())
+    rc = plan_dict_multi(ctx, B.dict_jobs.data(), (uint32_t)B.dict_jobs.size(), B.launches);
+  for (int mode = 0; mode < 2 && !rc; ++mode) {
+    std::vector<DecJob>& g = B.dec_jobs[mode];
+    if (g.empty()) continue;
+    uint64_t tiles = 0;
+    for (DecJob& j : g) {
+      j.tile0 = tiles;
+      tiles += (j.len + kVarintTile - 1) / kVarintTile;
+    }
+    const void* d = nullptr;
+    if (!(rc = stage_table(ctx, g.data(), g.size() * sizeof(DecJob), &d)))
+      B.launches.push_back(MultiLaunch{MultiLaunch::kDecimal, mode, d, (uint32_t)g.size(), tiles, 0});
+  }
+  if (rc) return fail_ctx(rc);
+  for (const ScanJob& j : B.scan_jobs) B.launches.push_back(MultiLaunch{MultiLaunch::kLengthScan, 0, &j, 1, 0, 0});
+  return ORCG_OK;
 }

@@ -8,7 +8,7 @@
 int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t in_count, const int64_t* rg_rows,
                         const uint64_t* d_in_count, Col* in_col) {
   Col& c = H->cols[id];
-  if (!selected[id] || !c.supported) return ORCG_OK;
+  if (!act.selected[id] || !c.supported) return ORCG_OK;
   // this column's kernels report into its own device error record
   struct Scope {
     orcg_reader* r;
@@ -16,11 +16,11 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
     unsigned long long* err;
     ~Scope() {
       r->cur_col = col;
-      r->ctx->d_err = err;
+      r->act.ctx->d_err = err;
     }
-  } scope{this, cur_col, ctx->d_err};
+  } scope{this, cur_col, act.ctx->d_err};
   cur_col = id;
-  ctx->d_err = D->d_errs + id;
+  act.ctx->d_err = D->d_errs + id;
   c.n = n;
   c.decoded = true;
   if (!c.stream_err.empty()) return fail(ORCG_PARSE_ERROR, c.stream_err);
@@ -36,7 +36,7 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
   c.converted = false;
   // schema evolution: a numeric or decimal column whose read type differs is
   // converted once its kind's decode has placed its rows
-  const bool convert = read && id < read->conv.size() && read->conv[id] == rt::kConvert;
+  const bool convert = act.read && id < act.read->conv.size() && act.read->conv[id] == rt::kConvert;
   auto then_convert = [&](int rc) { return rc || !convert ? rc : convert_column(id, c); };
   if (k == ORCG_TYPE_DECIMAL) return then_convert(decode_decimal(id, c, lay, r));
   if (is_timestamp_kind(k)) return decode_timestamp(c, lay, r);
@@ -149,8 +149,8 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
   const uint8_t* d_src = D->d_stage + sb.host_off;
   int64_t* base = nullptr;
   const uint64_t* total = nullptr;
-  const auto vp = varint_pre.find(id);
-  if (vp != varint_pre.end()) {
+  const auto vp = B.varint_pre.find(id);
+  if (vp != B.varint_pre.end()) {
     // tile counts + scan ran with the batch (queue_varint)
     base = vp->second.first;
     total = vp->second.second;
@@ -160,8 +160,8 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
     ORCG_ALLOC_TO(int64_t, base, sb.len / kVarintTile + 3);
     const uint64_t* h_total = nullptr;
     uint64_t* d_total = rb_alloc(1, &h_total);
-    if ((rc = launch_varint_tile_counts(ctx, d_src, sb.len, counts, &ntiles))) return fail_ctx(rc);
-    if ((rc = launch_exclusive_scan(ctx, counts, ntiles, base, nullptr, d_total))) return fail_ctx(rc);
+    if ((rc = launch_varint_tile_counts(act.ctx, d_src, sb.len, counts, &ntiles))) return fail_ctx(rc);
+    if ((rc = launch_exclusive_scan(act.ctx, counts, ntiles, base, nullptr, d_total))) return fail_ctx(rc);
     total = d_total ? h_total : defer(base + ntiles, 1);
     if (!total) return fail(ORCG_DEVICE_ERROR, "D2H of the varint count failed");
   }
@@ -170,8 +170,8 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
                                                          cid + " kind DATA")
                             : ORCG_OK;
   });
-  const auto dd = dec_done.find(id);
-  if (dd != dec_done.end() && !r.row_nn) {
+  const auto dd = B.dec_done.find(id);
+  if (dd != B.dec_done.end() && !r.row_nn) {
     // decoded by the batch's decimal launch (queue_decimal)
     c.data = dd->second;
     return ORCG_OK;
@@ -183,8 +183,9 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
   if (nullify) {
     ORCG_ALLOC_TO(uint8_t, keep, nonnull + 8);
   }
-  if ((rc = launch_varint_decimal(ctx, d_src, sb.len, base, scales, nonnull, hive11 ? hive11_scale : (int32_t)t.scale,
-                                  hive11 ? (nullify ? 3 : 2) : (wide ? 1 : 0), dense, keep)))
+  if ((rc = launch_varint_decimal(act.ctx, d_src, sb.len, base, scales, nonnull,
+                                  hive11 ? hive11_scale : (int32_t)t.scale, hive11 ? (nullify ? 3 : 2) : (wide ? 1 : 0),
+                                  dense, keep)))
     return fail_ctx(rc);
   if ((rc = place(dense, wide ? 16 : 8, n, &c.data))) return rc;
   return nullify && nonnull ? decode_hive11_nulls(c, keep, r) : ORCG_OK;
@@ -203,7 +204,7 @@ int orcg_reader::decode_hive11_nulls(Col& c, const uint8_t* keep, const Rows& r)
   const uint64_t* h_kept = nullptr;
   uint64_t* kept_d = rb_alloc(1, &h_kept);
   if (!kept_d) ORCG_ALLOC_TO(uint64_t, kept_d, 1);
-  if ((rc = launch_count_nonzero(ctx, rnn, n, kept_d))) return fail_ctx(rc);
+  if ((rc = launch_count_nonzero(act.ctx, rnn, n, kept_d))) return fail_ctx(rc);
   const uint64_t* kept = defer(kept_d, 1);
   if (!kept) return fail(ORCG_DEVICE_ERROR, "D2H of the kept decimal count failed");
   Col* cp = &c;
@@ -225,7 +226,7 @@ int orcg_reader::decode_hive11_nulls(Col& c, const uint8_t* keep, const Rows& r)
 // may be the parent's buffer: the kernel writes a new one.
 int orcg_reader::convert_column(uint32_t id, Col& c) {
   const TypeInfo& ft = footer.types[id];
-  const rt::Node& rn = read->tree[id];
+  const rt::Node& rn = act.read->tree[id];
   c.converted = true;
   c.rkind = rn.kind;
   c.rprecision = rn.precision;
@@ -258,9 +259,10 @@ int orcg_reader::convert_column(uint32_t id, Col& c) {
   uint64_t* slots = rb_alloc(2, &h);
   if (!slots) {
     ORCG_ALLOC_TO(uint64_t, slots, 2);
-    if ((rc = hip_check(ctx, hipMemsetAsync(slots, 0, 8, ctx->stream), "memset"))) return fail_ctx(rc);
+    if ((rc = hip_check(act.ctx, hipMemsetAsync(slots, 0, 8, act.ctx->stream), "memset"))) return fail_ctx(rc);
   }
-  if (evo_throw && (rc = hip_check(ctx, hipMemsetAsync(slots + 1, 0xff, 8, ctx->stream), "memset"))) return fail_ctx(rc);
+  if (act.evo_throw && (rc = hip_check(act.ctx, hipMemsetAsync(slots + 1, 0xff, 8, act.ctx->stream), "memset")))
+    return fail_ctx(rc);
   a.src = c.data;
   a.nn = c.has_nulls ? c.nn : nullptr;
   a.out = out;
@@ -271,19 +273,19 @@ int orcg_reader::convert_column(uint32_t id, Col& c) {
   a.src_scale = (int32_t)ft.scale;
   a.precision = (int32_t)rn.precision;
   a.scale = (int32_t)rn.scale;
-  a.throw_mode = evo_throw ? 1 : 0;
+  a.throw_mode = act.evo_throw ? 1 : 0;
   convert_constants(src, &a);
-  if ((rc = launch_convert(ctx, src, dst, a))) return fail_ctx(rc);
+  if ((rc = launch_convert(act.ctx, src, dst, a))) return fail_ctx(rc);
   if (!h && !(h = defer(slots, 2))) return fail(ORCG_DEVICE_ERROR, "D2H of the conversion's counts failed");
   c.data = out;
   if (c.has_nulls) c.nn = out_nn;  // the incoming nulls and the overflows
   Col* cp = &c;
   const uint64_t* rec = F->h_rb + cur_col;  // the column's own error record, read back with the stripe
-  const bool thrown = evo_throw;
-  const std::shared_ptr<const ReadPlan> plan = read;
+  const bool thrown = act.evo_throw;
+  const std::shared_ptr<const ReadPlan> plan = act.read;
   F->checks.emplace_back(cur_col, [this, cp, h, out_nn, rec, thrown, id, plan]() -> int {
     if (thrown && h[1] != kNoError && *rec == kNoError) {
-      if (ctx) ctx->last_error_value = h[1] >> 8;
+      if (act.ctx) act.ctx->last_error_value = h[1] >> 8;
       return fail(ORCG_PARSE_ERROR, std::string(dev_error_message(kErrConvertOverflow)) + " from " +
                                         rt::to_string(file_tree(), id) + " to " + rt::to_string(plan->tree, id));
     }
@@ -307,15 +309,15 @@ int orcg_reader::decode_timestamp(Col& c, const StreamLayout& lay, const Rows& r
   // TIMESTAMP_INSTANT ignores both zones; the same zone on both sides is
   // sameTimezone_ (:286): no adjustment, with that zone's epoch
   const ZoneEntry* wz = c.kind == ORCG_TYPE_TIMESTAMP ? H->writer_zone : nullptr;
-  if (wz && !reader_tz) return fail(ORCG_INVALID_ARGUMENT, "reader time zone not found");
-  if (wz && !reader_tz->zone) return fail(ORCG_PARSE_ERROR, reader_tz->err);
-  if (!wz || wz == reader_tz) {
-    if ((rc = launch_timestamp(ctx, secs, nanos, r.nonnull, wz ? wz->zone->epoch() : kOrcEpochUtc)))
+  if (wz && !act.reader_tz) return fail(ORCG_INVALID_ARGUMENT, "reader time zone not found");
+  if (wz && !act.reader_tz->zone) return fail(ORCG_PARSE_ERROR, act.reader_tz->err);
+  if (!wz || wz == act.reader_tz) {
+    if ((rc = launch_timestamp(act.ctx, secs, nanos, r.nonnull, wz ? wz->zone->epoch() : kOrcEpochUtc)))
       return fail_ctx(rc);
   } else {
     TzTable wt, rt;
-    if ((rc = zone_table(wz, &wt)) || (rc = zone_table(reader_tz, &rt))) return rc;
-    if ((rc = launch_timestamp_tz(ctx, secs, nanos, r.nonnull, wt, rt))) return fail_ctx(rc);
+    if ((rc = zone_table(wz, &wt)) || (rc = zone_table(act.reader_tz, &rt))) return rc;
+    if ((rc = launch_timestamp_tz(act.ctx, secs, nanos, r.nonnull, wt, rt))) return fail_ctx(rc);
   }
   if ((rc = place(secs, 8, r.n, &c.data))) return rc;
   return place(nanos, 8, r.n, &c.secondary);
@@ -337,7 +339,7 @@ int orcg_reader::decode_bytes(Col& c, const StreamLayout& lay, const Rows& r) {
   ORCG_ALLOC(uint8_t, bytes, r.nonnull + 8);
   if ((rc = byte_stream(c, *lay.find(kSlotData), r.nonnull, bytes))) return rc;
   ORCG_ALLOC(int64_t, dense, r.nonnull);
-  if ((rc = launch_widen(ctx, bytes, boolean ? kWidenU8 : kWidenI8, r.nonnull, dense))) return fail_ctx(rc);
+  if ((rc = launch_widen(act.ctx, bytes, boolean ? kWidenU8 : kWidenI8, r.nonnull, dense))) return fail_ctx(rc);
   return place(dense, 8, r.n, &c.data);
 }
 
@@ -350,7 +352,7 @@ int orcg_reader::decode_double(Col& c, const Rows& r) {
   double* dense;
   if (c.kind == ORCG_TYPE_FLOAT) {
     ORCG_ALLOC_TO(double, dense, r.nonnull);
-    const int rc = launch_widen(ctx, raw, kWidenF32, r.nonnull, dense);
+    const int rc = launch_widen(act.ctx, raw, kWidenF32, r.nonnull, dense);
     if (rc) return fail_ctx(rc);
   } else {
     dense = (double*)raw;  // zero copy: the stream bytes are the values
@@ -377,8 +379,8 @@ void orcg_reader::check_dictionary(uint32_t id, Col& c, const uint64_t* h) {
 
 int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay, const Rows& r) {
   const uint64_t n = r.n;
-  const auto dd = dict_done.find(id);
-  if (dd != dict_done.end()) {
+  const auto dd = B.dict_done.find(id);
+  if (dd != B.dict_done.end()) {
     // batched (queue_dict): offsets, summary and gather come from the
     // stripe's dictionary launch; the reference's checks, in its order
     check_dictionary(id, c, dd->second.h_summary);
@@ -391,7 +393,7 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
   int rc;
   int64_t* start = nullptr;
   int64_t* len = nullptr;
-  if (!lazy_dict) {
+  if (!act.lazy_dict) {
     ORCG_ALLOC_TO(int64_t, start, n);
     ORCG_ALLOC_TO(int64_t, len, n);
   }
@@ -402,12 +404,13 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
     return fail(ORCG_PARSE_ERROR, "LENGTH stream not found in StringDictionaryColumn for column " + std::to_string(id));
   int64_t* doff;
   const uint64_t* h;
-  const auto pre = dict_pre.find(id);
-  if (pre != dict_pre.end()) {
+  const auto pre = B.dict_pre.find(id);
+  if (pre != B.dict_pre.end()) {
     // offsets and summary from the stripe's dictionary launch (collect_dicts)
     doff = pre->second.offsets;
     h = pre->second.h_summary;
-    if (pre_on_lane && (rc = hip_check(ctx, hipStreamWaitEvent(ctx->stream, ev_pre, 0), "dictionary batch wait")))
+    if (B.pre_on_lane &&
+        (rc = hip_check(act.ctx, hipStreamWaitEvent(act.ctx->stream, B.ev_pre, 0), "dictionary batch wait")))
       return fail_ctx(rc);
   } else {
     int64_t* dlen;
@@ -418,11 +421,12 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
     if (!summary) ORCG_ALLOC_TO(uint64_t, summary, 2);
     if (dict_size <= 65536) {
       // offsets, blob size and the negative-length check in one launch
-      if ((rc = launch_dict_offsets(ctx, dlen, dict_size, doff, summary))) return fail_ctx(rc);
+      if ((rc = launch_dict_offsets(act.ctx, dlen, dict_size, doff, summary))) return fail_ctx(rc);
     } else {
-      if ((rc = launch_flag_negative(ctx, dlen, dict_size, summary + 1))) return fail_ctx(rc);
-      if ((rc = launch_exclusive_scan(ctx, dlen, dict_size, doff))) return fail_ctx(rc);
-      if ((rc = hip_check(ctx, hipMemcpyAsync(summary, doff + dict_size, 8, hipMemcpyDeviceToDevice, ctx->stream),
+      if ((rc = launch_flag_negative(act.ctx, dlen, dict_size, summary + 1))) return fail_ctx(rc);
+      if ((rc = launch_exclusive_scan(act.ctx, dlen, dict_size, doff))) return fail_ctx(rc);
+      if ((rc = hip_check(act.ctx,
+                          hipMemcpyAsync(summary, doff + dict_size, 8, hipMemcpyDeviceToDevice, act.ctx->stream),
                           "copy")))
         return fail_ctx(rc);
     }
@@ -436,14 +440,14 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
   if ((rc = place(idx, 8, n, &ridx))) return rc;
   c.index = ridx;
   c.dict_offsets = doff;
-  if (!lazy_dict) {
+  if (!act.lazy_dict) {
     // StringDictionaryColumnReader::next: bounds-checked gather; nextEncoded
     // (lazy) hands out the indices and the dictionary unchecked (:596-607)
     if (r.row_nn) {
-      if ((rc = hip_check(ctx, hipMemsetAsync(start, 0, n * 8, ctx->stream), "memset"))) return fail_ctx(rc);
-      if ((rc = hip_check(ctx, hipMemsetAsync(len, 0, n * 8, ctx->stream), "memset"))) return fail_ctx(rc);
+      if ((rc = hip_check(act.ctx, hipMemsetAsync(start, 0, n * 8, act.ctx->stream), "memset"))) return fail_ctx(rc);
+      if ((rc = hip_check(act.ctx, hipMemsetAsync(len, 0, n * 8, act.ctx->stream), "memset"))) return fail_ctx(rc);
     }
-    if ((rc = launch_dict_gather(ctx, ridx, 8, r.row_nn, n, doff, dict_size, start, len))) return fail_ctx(rc);
+    if ((rc = launch_dict_gather(act.ctx, ridx, 8, r.row_nn, n, doff, dict_size, start, len))) return fail_ctx(rc);
   }
   c.data = start;
   c.length = len;
@@ -461,8 +465,8 @@ int orcg_reader::decode_direct_string(uint32_t id, Col& c, const StreamLayout& l
   // negative length, the total's overflow (then the blob's size below),
   // in the reference's order; the flags start at 0 (read-back block).
   // The batch's scan (queue_scan) already ran for a column without nulls.
-  const auto sd = scan_done.find(id);
-  const bool pre = sd != scan_done.end() && !r.row_nn && sd->second.n == ns;
+  const auto sd = B.scan_done.find(id);
+  const bool pre = sd != B.scan_done.end() && !r.row_nn && sd->second.n == ns;
   int64_t* dstart = nullptr;
   const uint64_t* h_fl = nullptr;
   const uint64_t* need = nullptr;
@@ -476,10 +480,10 @@ int orcg_reader::decode_direct_string(uint32_t id, Col& c, const StreamLayout& l
     flags = rb_alloc(2, &h_fl);
     if (!flags) {
       ORCG_ALLOC_TO(uint64_t, flags, 2);
-      if ((rc = hip_check(ctx, hipMemsetAsync(flags, 0, 16, ctx->stream), "flags memset"))) return fail_ctx(rc);
+      if ((rc = hip_check(act.ctx, hipMemsetAsync(flags, 0, 16, act.ctx->stream), "flags memset"))) return fail_ctx(rc);
     }
     uint64_t* d_need = rb_alloc(1, &need);
-    if ((rc = launch_exclusive_scan(ctx, dlen, ns, dstart, flags, d_need))) return fail_ctx(rc);
+    if ((rc = launch_exclusive_scan(act.ctx, dlen, ns, dstart, flags, d_need))) return fail_ctx(rc);
   }
   StreamBuf& db = c.s[kSlotData];
   c.blob = D->d_stage + db.host_off;
@@ -511,19 +515,19 @@ int orcg_reader::decode_list(uint32_t id, Col& c, const StreamLayout& lay, const
   if ((rc = int_stream(c, *lay.find(kSlotLength), r.nonnull, &dlen, r.d_nonnull))) return rc;
   if ((rc = place(dlen, 8, n, &rlen))) return rc;
   ORCG_ALLOC(int64_t, off, n + 1);
-  if ((rc = launch_exclusive_scan(ctx, rlen, n, off))) return fail_ctx(rc);
+  if ((rc = launch_exclusive_scan(act.ctx, rlen, n, off))) return fail_ctx(rc);
   c.offsets = off;
   // the children's row groups start at the list offsets of the parent's
   int64_t* child_rows = nullptr;
   if (r.rg_rows && H->ngroups) {
     ORCG_ALLOC_TO(int64_t, child_rows, H->ngroups);
-    if ((rc = launch_rg_child_rows(ctx, off, r.rg_rows, H->ngroups, child_rows))) return fail_ctx(rc);
+    if ((rc = launch_rg_child_rows(act.ctx, off, r.rg_rows, H->ngroups, child_rows))) return fail_ctx(rc);
   }
   if (pending) {
     // under a fork: the children wait for the fork's next level, whose
     // element counts are read back together (one synchronisation per level
     // instead of one per list / map, which would stall the other lanes)
-    pending->push_back(Pending{id, off + n, child_rows, ctx});
+    pending->push_back(Pending{id, off + n, child_rows, act.ctx});
     return ORCG_OK;
   }
   uint64_t total = 0;
@@ -545,7 +549,7 @@ int orcg_reader::decode_union(uint32_t id, Col& c, const StreamLayout& lay, cons
   ORCG_ALLOC(uint8_t, dtags, nonnull + 8);
   if ((rc = byte_stream(c, *lay.find(kSlotData), nonnull, dtags))) return rc;
   ORCG_ALLOC(uint64_t, bad, 1);
-  if ((rc = launch_union_check(ctx, dtags, nonnull, nch, bad))) return fail_ctx(rc);
+  if ((rc = launch_union_check(act.ctx, dtags, nonnull, nch, bad))) return fail_ctx(rc);
   ORCG_ALLOC(int64_t, doffs, nonnull);
   ORCG_ALLOC(int64_t, flags, nonnull);
   // dense index of each row group's first row (children's row groups)
@@ -553,20 +557,20 @@ int orcg_reader::decode_union(uint32_t id, Col& c, const StreamLayout& lay, cons
   if (r.rg_rows && H->ngroups && r.row_nn) {
     ORCG_ALLOC(int64_t, cnt, H->ngroups);
     ORCG_ALLOC(int64_t, pre, H->ngroups + 1);
-    if ((rc = launch_rg_prefix(ctx, r.row_nn, n, r.rg_rows, H->ngroups, cnt, pre))) return fail_ctx(rc);
+    if ((rc = launch_rg_prefix(act.ctx, r.row_nn, n, r.rg_rows, H->ngroups, cnt, pre))) return fail_ctx(rc);
     dense_rows = pre;
   }
   std::vector<int64_t*> scans(nch, nullptr);
   std::vector<CountSrc> rb;  // per child its row count, then the first bad tag
   for (uint32_t kk = 0; kk < nch; ++kk) {
     ORCG_ALLOC_TO(int64_t, scans[kk], nonnull + 1);
-    if ((rc = launch_union_flags(ctx, dtags, nonnull, kk, flags)) ||
-        (rc = launch_exclusive_scan(ctx, flags, nonnull, scans[kk])) ||
-        (rc = launch_union_offsets(ctx, dtags, nonnull, kk, scans[kk], doffs)))
+    if ((rc = launch_union_flags(act.ctx, dtags, nonnull, kk, flags)) ||
+        (rc = launch_exclusive_scan(act.ctx, flags, nonnull, scans[kk])) ||
+        (rc = launch_union_offsets(act.ctx, dtags, nonnull, kk, scans[kk], doffs)))
       return fail_ctx(rc);
-    rb.push_back(CountSrc{ctx, scans[kk] + nonnull});
+    rb.push_back(CountSrc{act.ctx, scans[kk] + nonnull});
   }
-  rb.push_back(CountSrc{ctx, bad});
+  rb.push_back(CountSrc{act.ctx, bad});
   std::vector<uint64_t> counts(nch + 1, 0);
   if ((rc = read_back(rb, counts.data()))) return rc;
   const uint64_t first_bad = counts[nch];
@@ -578,7 +582,7 @@ int orcg_reader::decode_union(uint32_t id, Col& c, const StreamLayout& lay, cons
     int64_t* child_rows = nullptr;
     if (dense_rows && H->ngroups) {
       ORCG_ALLOC_TO(int64_t, child_rows, H->ngroups);
-      if ((rc = launch_rg_child_rows(ctx, scans[kk], dense_rows, H->ngroups, child_rows))) return fail_ctx(rc);
+      if ((rc = launch_rg_child_rows(act.ctx, scans[kk], dense_rows, H->ngroups, child_rows))) return fail_ctx(rc);
     }
     if ((rc = decode(subs[kk], counts[kk], nullptr, counts[kk], child_rows))) return rc;
   }

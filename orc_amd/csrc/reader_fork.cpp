@@ -6,7 +6,7 @@ int orcg_reader::decode_struct(uint32_t id, Col& c, const Rows& r) {
   std::vector<uint32_t> kids;
   size_t busy = 0;  // subtrees with launches of their own (the rest only wire batched outputs)
   for (uint32_t st : footer.types[id].subtypes)
-    if (selected[st] && H->cols[st].supported) {
+    if (act.selected[st] && H->cols[st].supported) {
       kids.push_back(st);
       busy += device_work(st) ? 1 : 0;
     }
@@ -26,9 +26,9 @@ int orcg_reader::decode_struct(uint32_t id, Col& c, const Rows& r) {
 // reads their outputs
 int orcg_reader::fork_struct(Col& c, const std::vector<uint32_t>& kids, unsigned nl, const Rows& r) {
   int rc = ORCG_OK;
-  Ctx* base = ctx;
+  Ctx* base = act.ctx;
   if (!ctx_lane(base, 0)) return fail(ORCG_DEVICE_ERROR, "side stream creation failed");
-  if ((rc = hip_check(ctx, hipEventRecord(base->ev_fork, base->stream), "fork event"))) return fail_ctx(rc);
+  if ((rc = hip_check(act.ctx, hipEventRecord(base->ev_fork, base->stream), "fork event"))) return fail_ctx(rc);
   std::vector<uint8_t> used(nl, 0);
   std::vector<Pending> level;  // lists / maps whose children wait for their element counts
   pending = &level;
@@ -45,11 +45,11 @@ int orcg_reader::fork_struct(Col& c, const std::vector<uint32_t>& kids, unsigned
         break;
       }
     }
-    ctx = L;
+    act.ctx = L;
     in_lane = true;
     rc = decode(kids[j], r.n, c.nn, r.nonnull, r.rg_rows, c.nn ? r.d_nonnull : nullptr, &c);
     in_lane = false;
-    ctx = base;
+    act.ctx = base;
   }
   rc = fork_levels(base, nl, used, level, rc);
   pending = nullptr;
@@ -80,7 +80,7 @@ int orcg_reader::fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used,
   std::string fail_msg = fork_rc ? fork_msg : std::string();
   int hard = ORCG_OK;  // a failure outside any column's decode: stop
   std::function<uint32_t(uint32_t)> cols_in = [&](uint32_t t) -> uint32_t {
-    uint32_t k = selected[t] && H->cols[t].supported ? 1u : 0u;
+    uint32_t k = act.selected[t] && H->cols[t].supported ? 1u : 0u;
     for (uint32_t st : footer.types[t].subtypes) k += cols_in(st);
     return k;
   };
@@ -131,11 +131,11 @@ int orcg_reader::fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used,
       err_col = kNoCol;
       int lr = ORCG_OK;
       for (size_t si = 0; si < subs.size() && !lr; ++si) {
-        ctx = on[si];
+        act.ctx = on[si];
         lr = decode(subs[si], totals[q], nullptr, totals[q], cur[q].child_rows);
       }
       in_lane = false;
-      ctx = base;
+      act.ctx = base;
       if (lr) {
         const uint32_t ec = err_col != kNoCol ? err_col : cur[q].id;
         if (ec < fail_col) {
@@ -152,7 +152,7 @@ int orcg_reader::fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used,
     rc = fail_rc;
     err_col = fail_col;
     last_error = fail_msg;
-    ctx->last_error = fail_msg;
+    act.ctx->last_error = fail_msg;
   }
   return rc;
 }

@@ -30,6 +30,7 @@
 #include <memory>
 #include <mutex>
 #include <thread>
+#include <unordered_map>
 
 #include "../../include/orcg_reader.h"
 #include "orc_file.hh"
@@ -222,6 +223,32 @@ struct ReadPlan {
   std::string text;
 };
 
+// What a read is asked for (RowReaderOptions, and this reader's own
+// switches): the reader holds its own, changed by the setters; a row reader
+// holds the snapshot of its creation, immutable from then on. The decode in
+// progress works on a copy (orcg_reader::act, made by Active under the
+// reader's mutex) rather than a pointer to the caller's: the copy is what a
+// struct's fork points at a side lane (ctx) and where a reader zone left
+// unset resolves to GMT, neither of which may touch the caller's options;
+// it costs an assignment into members that keep their capacity.
+struct ReadOptions {
+  Ctx* ctx = nullptr;             // the context the decode launches on
+  std::vector<uint8_t> selected;  // RowReaderOptions::include, per type id
+  bool lazy_dict = false;         // dictionary strings stay encoded (index + dictionary)
+  // Time zones: the reader's (RowReaderOptions::setTimezoneName; nullptr:
+  // "GMT"), and the zone assumed for stripes that name none
+  const ZoneEntry* reader_tz = nullptr;
+  std::string local_tz;
+  // Schema evolution (RowReaderOptions::setReadType /
+  // throwOnSchemaEvolutionOverflow). A plan is immutable once set; row
+  // readers share it.
+  std::shared_ptr<const ReadPlan> read;
+  bool evo_throw = false;
+  // orcg_reader_set_device_decompression: Snappy chunks of raw byte streams
+  // ride the upload compressed and inflate on the device
+  bool dev_inflate = false;
+};
+
 // A column of a stripe being prepared and decoded: its streams, and the view
 // the decode fills
 struct Col : ColView {
@@ -341,6 +368,97 @@ inline uint64_t v1_segments(const HostStage& hs) {
   return n;
 }
 
+// A stripe's multi-stream batch: before decode(), the streams whose value
+// counts and segments are known without device results (columns with no
+// PRESENT stream, under parents with none), and what hangs off them, are
+// queued here and decoded by one launch per kernel instance (run_multi);
+// decode() then finds their outputs here. One per reader, reused by every
+// stripe: a new table is added to reset() and nowhere else.
+struct StripeBatch {
+  std::vector<RleJob> rlev2;       // RLEv2 streams
+  std::vector<V1SegDesc> v1_segs;  // RLEv1 streams' segments
+  // batched integer streams by (column, slot): their values and count
+  struct Values {
+    int64_t* values;
+    uint64_t count;
+  };
+  std::unordered_map<uint64_t, Values> batched;
+  const Values* find(uint32_t id, int slot) const {
+    const auto it = batched.find(key(id, slot));
+    return it == batched.end() ? nullptr : &it->second;
+  }
+  void put(uint32_t id, int slot, int64_t* values, uint64_t count) { batched[key(id, slot)] = Values{values, count}; }
+  // dictionary columns of the batch (no nulls, <= kDictLds entries): their
+  // offsets and gathers in one launch after the streams (dict_multi_kernel)
+  struct DictDone {
+    int64_t* offsets;
+    const uint64_t* h_summary;
+    int64_t* start;
+    int64_t* len;
+    int64_t* idx;
+  };
+  std::vector<DictJob> dict_jobs;
+  std::unordered_map<uint32_t, DictDone> dict_done;
+  // dictionaries of columns the batch cannot take whole (nullable, under a
+  // list / map): their entry offsets and summary only, from the same launch
+  std::unordered_map<uint32_t, DictDone> dict_pre;
+  // a batch of such dictionaries only runs on side lane 0 (issue()); the
+  // gathers reading its offsets and the stripe's read-back wait on ev_pre
+  hipEvent_t ev_pre = nullptr;
+  bool pre_on_lane = false;
+  // varint decimal DATA streams whose tile counts + scan run with the batch
+  // (before its join): their tile bases and value-count slots by column.
+  // (varint_jobs and scan_jobs are deques: `launches` points at their
+  // elements, whose addresses a later push must not move)
+  std::deque<VarintJob> varint_jobs;
+  std::unordered_map<uint32_t, std::pair<int64_t*, const uint64_t*>> varint_pre;
+  // varint decimal columns (no nulls, not Hive 0.11) decoded by one launch
+  // per mode after the batch's join (varint_decimal_multi_kernel)
+  std::vector<DecJob> dec_jobs[2];
+  std::unordered_map<uint32_t, void*> dec_done;
+  // direct string columns (no nulls) whose length scan runs after the
+  // batch's join, beside the dictionaries and decimals
+  struct ScanDone {
+    int64_t* starts;
+    const uint64_t* h_flags;
+    const uint64_t* h_need;
+    uint64_t n;
+  };
+  std::deque<ScanJob> scan_jobs;
+  std::unordered_map<uint32_t, ScanDone> scan_done;
+  std::vector<MultiLaunch> launches;
+
+  // empties every table for the next stripe and keeps its capacity
+  // (configs[0] reads thousands of 5,000-row stripes)
+  void reset() {
+    rlev2.clear();
+    v1_segs.clear();
+    batched.clear();
+    dict_jobs.clear();
+    dict_done.clear();
+    dict_pre.clear();
+    varint_jobs.clear();
+    varint_pre.clear();
+    dec_jobs[0].clear();
+    dec_jobs[1].clear();
+    dec_done.clear();
+    scan_jobs.clear();
+    scan_done.clear();
+    launches.clear();
+    pre_on_lane = false;
+  }
+  // Holds only pre-loaded dictionaries (collect_dicts: every batched stream
+  // is such a dictionary's LENGTH): nothing reads the batch's outputs before
+  // a fork's next level
+  bool only_preloaded_dicts() const {
+    return batched.size() == dict_pre.size() && dict_done.empty() && scan_jobs.empty() && dec_jobs[0].empty() &&
+           dec_jobs[1].empty() && varint_jobs.empty();
+  }
+
+ private:
+  static uint64_t key(uint32_t id, int slot) { return (uint64_t)id * 8 + (uint64_t)slot; }
+};
+
 }  // namespace reader
 }  // namespace orcg
 
@@ -352,32 +470,19 @@ struct orcg_reader {
   // serialises decodes: the reader's own reads and the row readers' prefetch
   // workers share its decode state (stages, batch tables, checks)
   std::mutex mu;
-  // The reader's own options: its context (fixed at open), its column
-  // selection and lazy-dictionary flag (changed under mu). Entry points that
-  // run outside a decode (copy_to_host, is_selected, row reader creation)
-  // read only these; a row reader's worker never writes them.
-  Ctx* own_ctx = nullptr;
-  std::vector<uint8_t> own_sel;  // per type id
-  bool own_lazy = false;
-  // orcg_reader_set_device_decompression: Snappy chunks of raw byte streams
-  // ride the upload compressed and inflate on the device. The reader's own,
-  // and that of the decode in progress (a row reader's copy)
-  bool own_dev_inflate = false, dev_inflate = false;
-  uint64_t last_dev_inflate[2] = {0, 0};  // last read: chunks, decompressed bytes inflated on the device
+  // The reader's own options (changed by the setters under mu; the context
+  // is fixed at open). Entry points that run outside a decode (copy_to_host,
+  // is_selected, row reader creation, the Arrow export) read only these; a
+  // row reader's worker never writes them.
+  ReadOptions own;
   // The options of the decode in progress (valid under mu, set by Active):
   // the reader's own for its reads, a row reader's for that row reader's
-  // prefetch decodes.
-  Ctx* ctx = nullptr;
-  std::vector<uint8_t> selected;
-  bool lazy_dict = false;
-  // Time zones (RowReaderOptions::setTimezoneName, default "GMT"; the zone
-  // assumed for stripes that name none): the reader's own, and those of the
-  // decode in progress. Resolved zones live as long as the reader (zones,
-  // under tz_mu: prepare() resolves writer zones on worker threads).
-  const ZoneEntry* own_reader_tz = nullptr;  // nullptr: the built-in UTC zone
-  std::string own_local_tz;
-  const ZoneEntry* reader_tz = nullptr;
-  std::string local_tz;
+  // prefetch decodes. act.ctx is the context the decode launches on: null
+  // outside a decode, and within a struct's fork a side lane of the caller's.
+  ReadOptions act;
+  uint64_t last_dev_inflate[2] = {0, 0};  // last read: chunks, decompressed bytes inflated on the device
+  // Resolved zones live as long as the reader (zones, under tz_mu: prepare()
+  // resolves writer zones on worker threads).
   mutable std::mutex tz_mu;
   mutable std::map<std::string, std::unique_ptr<ZoneEntry>> zones;  // by canonical name
   mutable std::vector<std::unique_ptr<ZoneEntry>> zones_replaced;   // entries set_zone_rules replaced
@@ -385,27 +490,16 @@ struct orcg_reader {
   const ZoneEntry* utc_zone_entry() const;                       // caller holds tz_mu
   const ZoneEntry* resolve_zone(const std::string& name) const;  // NULL: not found
   int zone_table(const ZoneEntry* z, TzTable* out);
-  // Schema evolution (RowReaderOptions::setReadType /
-  // throwOnSchemaEvolutionOverflow): the reader's own, and those of the decode
-  // in progress. A plan is immutable once set; row readers share it.
-  std::shared_ptr<const ReadPlan> own_read, read;
-  bool own_evo_throw = false, evo_throw = false;
   rt::Tree file_tree() const;  // the file's types as read_type.hh's tree
+  // Makes `o` the options of the decode in progress, for its scope (the
+  // caller holds mu). A reader zone left unset resolves to "GMT" here.
   struct Active {
     orcg_reader* r;
-    Active(orcg_reader* r_, Ctx* c, const std::vector<uint8_t>& sel, bool lazy, const ZoneEntry* rtz,
-           const std::string& ltz, std::shared_ptr<const ReadPlan> rd, bool evo, bool dev_inflate)
-        : r(r_) {
-      r->dev_inflate = dev_inflate;
-      r->read = std::move(rd);
-      r->evo_throw = evo;
-      r->ctx = c;
-      r->selected = sel;
-      r->lazy_dict = lazy;
-      r->reader_tz = rtz ? rtz : r->resolve_zone("GMT");
-      r->local_tz = ltz;
+    Active(orcg_reader* r_, const ReadOptions& o) : r(r_) {
+      r->act = o;
+      if (!r->act.reader_tz) r->act.reader_tz = r->resolve_zone("GMT");
     }
-    ~Active() { r->ctx = nullptr; }
+    ~Active() { r->act.ctx = nullptr; }
   };
   const uint8_t* file = nullptr;
   uint64_t file_len = 0;
@@ -449,14 +543,14 @@ struct orcg_reader {
     ev_pool.pop_back();
     return e;
   }
-  // brackets the launches `f` enqueues on ctx->stream with a timed event pair
+  // brackets the launches `f` enqueues on act.ctx->stream with a timed event pair
   template <class Fn>
   int timed(int kind, Fn&& f) {
     if (!metrics_timing) return f();
     hipEvent_t a = ev_get(), b = ev_get();
-    if (a) (void)hipEventRecord(a, ctx->stream);
+    if (a) (void)hipEventRecord(a, act.ctx->stream);
     const int rc = f();
-    if (b) (void)hipEventRecord(b, ctx->stream);
+    if (b) (void)hipEventRecord(b, act.ctx->stream);
     if (a && b) F->ev_used.push_back(EvPair{a, b, kind});
     else {
       if (a) ev_pool.push_back(a);
@@ -534,7 +628,7 @@ struct orcg_reader {
     if (F->defer_used + count > F->defer_cap) return nullptr;
     uint64_t* h = F->h_defer + F->defer_used;
     F->defer_used += count;
-    if (hipMemcpyAsync(h, d_src, count * 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) return nullptr;
+    if (hipMemcpyAsync(h, d_src, count * 8, hipMemcpyDeviceToHost, act.ctx->stream) != hipSuccess) return nullptr;
     return h;
   }
 
@@ -560,22 +654,22 @@ struct orcg_reader {
   // poll_counts, else the D2H copies on each source's stream and one
   // synchronisation per stream used
   int read_back(const std::vector<CountSrc>& srcs, uint64_t* out);
-  int read_back(const void* src, uint64_t* out) { return read_back({CountSrc{ctx, src}}, out); }
+  int read_back(const void* src, uint64_t* out) { return read_back({CountSrc{act.ctx, src}}, out); }
 
   ~orcg_reader();  // reader_api.cpp
   int fail(int status, const std::string& m) {
     if (err_col == kNoCol) err_col = cur_col;
     last_error = m;
-    if (ctx) ctx->last_error = m;
+    if (act.ctx) act.ctx->last_error = m;
     return status;
   }
-  int fail_ctx(int rc) { return fail(rc, ctx ? ctx->last_error : std::string("device error")); }
+  int fail_ctx(int rc) { return fail(rc, act.ctx ? act.ctx->last_error : std::string("device error")); }
   // a failure outside a decode (argument F->checks of the caller's thread):
   // last_error is shared with the row readers' workers, so under mu
   int fail_user(int status, const std::string& m) {
     std::lock_guard<std::mutex> lk(mu);
     last_error = m;
-    if (own_ctx) own_ctx->last_error = m;
+    if (own.ctx) own.ctx->last_error = m;
     return status;
   }
   int fail_oom(const char* file, int line) {
@@ -584,11 +678,10 @@ struct orcg_reader {
   }
 
   int open_tail();
-  // (sel: the column selection of the read it prepares for; prepare reads
-  // nothing else the decodes change, so it runs without mu)
-  int prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& sel, const std::string& local_zone,
-              bool device_inflate) const;
-  int prepare(uint64_t s, HostStage& hs) const { return prepare(s, hs, selected, local_tz, dev_inflate); }
+  // (o: the options of the read it prepares for, of which it reads only the
+  // selection, the local zone and the device-inflate flag, and nothing else
+  // the decodes change: it runs without mu, beside a decode)
+  int prepare(uint64_t s, HostStage& hs, const ReadOptions& o) const;
   // whether the stripe's stream (col, slot) is one the host never walks: raw
   // bytes or varints, which a Snappy file's chunks can inflate on the device
   bool host_never_walks(const HostStage& hs, uint32_t col, int slot) const;
@@ -686,59 +779,24 @@ struct orcg_reader {
   // when collect() queued it, else allocated and decoded now)
   // (dcount: the value count on the device, `count` then only sizes the output)
   int int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t** out, const uint64_t* dcount = nullptr);
-  // Multi-stream batch: before decode(), the RLEv2 streams whose value
-  // counts and segments are known without device results (columns with no
-  // PRESENT stream, under parents with none) are queued and decoded by one
-  // launch per kernel instance (launch_rlev2_multi); decode() then finds
-  // their outputs here.
+  // The stripe's multi-stream batch (StripeBatch): collect() queues what
+  // the host can count before the upload, plan_batch() turns the queues into
+  // launches, and decode() then finds the outputs in B.
   bool batch_on = true;
-  std::vector<RleJob> batch;          // RLEv2 streams
-  std::vector<V1SegDesc> v1_segs;     // RLEv1 streams' segments
-  // dictionary columns of the batch (no nulls, <= kDictLds entries): their
-  // offsets and gathers in one launch after the streams (dict_multi_kernel)
-  struct DictDone {
-    int64_t* offsets;
-    const uint64_t* h_summary;
-    int64_t* start;
-    int64_t* len;
-    int64_t* idx;
-  };
-  std::vector<DictJob> dict_batch;
-  std::unordered_map<uint32_t, DictDone> dict_done;
-  // dictionaries of columns the batch cannot take whole (nullable, under a
-  // list / map): their entry offsets and summary only, from the same launch
-  std::unordered_map<uint32_t, DictDone> dict_pre;
+  StripeBatch B;
+  int collect(uint32_t id, uint64_t n, const int64_t* rg_rows);
   int collect_dicts(uint32_t id);
-  // a batch of such dictionaries only runs on side lane 0 (issue()); the
-  // gathers reading its offsets and the stripe's read-back wait on ev_pre
-  hipEvent_t ev_pre = nullptr;
-  bool pre_on_lane = false;
-  // varint decimal DATA streams whose tile counts + scan run with the batch
-  // (before its join): their tile bases and value-count slots by column
-  std::deque<VarintJob> varint_jobs;
-  std::unordered_map<uint32_t, std::pair<int64_t*, const uint64_t*>> varint_pre;
-  int queue_varint(uint32_t id);
-  // varint decimal columns (no nulls, not Hive 0.11) decoded by one launch
-  // per mode after the batch's join (varint_decimal_multi_kernel)
-  std::vector<DecJob> dec_batch[2];
-  std::unordered_map<uint32_t, void*> dec_done;
-  int queue_decimal(uint32_t id, uint64_t n);
-  // direct string columns (no nulls) whose length scan runs after the
-  // batch's join, beside the dictionaries and decimals
-  struct ScanDone {
-    int64_t* starts;
-    const uint64_t* h_flags;
-    const uint64_t* h_need;
-    uint64_t n;
-  };
-  std::deque<ScanJob> scan_jobs;
-  std::unordered_map<uint32_t, ScanDone> scan_done;
-  int queue_scan(uint32_t id, uint64_t n);
-  std::vector<MultiLaunch> launches;
-  std::unordered_map<uint64_t, std::pair<int64_t*, uint64_t>> batched;  // (column, slot) -> (values, count)
   int queue_stream(uint32_t id, const StreamDesc& d, uint64_t count);
   int queue_dict(uint32_t id, uint64_t n);
-  int collect(uint32_t id, uint64_t n, const int64_t* rg_rows);
+  int queue_varint(uint32_t id);
+  int queue_decimal(uint32_t id, uint64_t n);
+  int queue_scan(uint32_t id, uint64_t n);
+  // the job queue_dict and collect_dicts both queue: column id's dictionary
+  // (entry offsets and summary; with `gather`, the n rows' starts and
+  // lengths too), recorded in `done` (B.dict_done or B.dict_pre)
+  int push_dict(uint32_t id, const int64_t* lengths, const int64_t* idx, uint64_t n, bool gather,
+                std::unordered_map<uint32_t, StripeBatch::DictDone>& done);
+  int plan_batch();
   int byte_stream(Col& c, const StreamDesc& d, uint64_t count, uint8_t* out, uint64_t* d_ones = nullptr,
                   const uint64_t* d_count = nullptr);
   int scatter(const void* dense, const uint8_t* nn, uint64_t n, void* out, int width);

@@ -48,7 +48,7 @@ int orcg_reader::open_tail() {
                                           std::to_string(j) + ") in types(" + std::to_string(i) + ")");
     }
   }
-  own_sel.assign(nt, 1);
+  own.selected.assign(nt, 1);
   return ORCG_OK;
 }
 
@@ -538,8 +538,7 @@ bool orcg_reader::host_never_walks(const HostStage& hs, uint32_t col, int slot) 
   return d && (d->coding == kRaw || d->coding == kVarint);
 }
 
-int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& selected,
-                         const std::string& local_zone, bool device_inflate) const {
+int orcg_reader::prepare(uint64_t s, HostStage& hs, const ReadOptions& o) const {
   hs.stripe = s;
   hs.inflate.clear();
   hs.inflate_off = hs.tail_off = hs.tail_bytes = 0;
@@ -549,11 +548,11 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
   StripeFooter sf;
   std::vector<int> row_index;
   std::vector<Need> needs;
-  int rc = locate_streams(s, hs, selected, local_zone, sf, row_index, needs);
+  int rc = locate_streams(s, hs, o.selected, o.local_tz, sf, row_index, needs);
   if (rc) return rc;
   // Snappy chunks of the streams the host never walks inflate on the device
   // (a block size past the kernel's 32-bit offsets keeps the host path)
-  if (device_inflate && ps.compression == kSnappy && ps.block_size < kSnappyMaxBytes)
+  if (o.dev_inflate && ps.compression == kSnappy && ps.block_size < kSnappyMaxBytes)
     for (Need& nd : needs) nd.device = host_never_walks(hs, nd.col, nd.slot);
   double t1 = 0;
   uint64_t w = 0;
@@ -561,7 +560,7 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const std::vector<uint8_t>& 
   const double t15 = now_s();
   map_row_index(s, sf, row_index, needs, hs);
   std::vector<StreamBuf*> rle;
-  build_plans(selected, hs, rle);
+  build_plans(o.selected, hs, rle);
   if ((rc = layout_staging(s, hs, rle, w))) return rc;
   if (!hs.inflate.empty()) {
     // the tail: past everything issue() uploads (used + slack bounds it)

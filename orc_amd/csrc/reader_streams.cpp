@@ -3,7 +3,7 @@
 #include "reader_internal.hh"
 
 int orcg_reader::scatter(const void* dense, const uint8_t* nn, uint64_t n, void* out, int width) {
-  return launch_scatter(ctx, dense, nn, n, out, width, 1, 0);
+  return launch_scatter(act.ctx, dense, nn, n, out, width, 1, 0);
 }
 
 int orcg_reader::place_bytes(const void* dense, int width, uint64_t count, void** out) {
@@ -33,7 +33,7 @@ int orcg_reader::segments(Col& c, int slot, bool boolean, const uint64_t** d_seg
     // the row groups' set-row prefix and the segment table in one launch
     ORCG_ALLOC(int64_t, pre, G + 1);
     ORCG_ALLOC(uint64_t, seg, 2 * G);
-    if ((rc = launch_rg_prefix_segtab(ctx, mask, cur_n, cur_rows, G, (const int64_t*)(D->d_stage + sb.rg_off), boolean,
+    if ((rc = launch_rg_prefix_segtab(act.ctx, mask, cur_n, cur_rows, G, (const int64_t*)(D->d_stage + sb.rg_off), boolean,
                                       pre, seg)))
       return fail_ctx(rc);
     *d_seg = seg;
@@ -41,7 +41,7 @@ int orcg_reader::segments(Col& c, int slot, bool boolean, const uint64_t** d_seg
     return ORCG_OK;
   }
   ORCG_ALLOC(uint64_t, seg, 2 * G);
-  if ((rc = launch_rg_segtab(ctx, (const int64_t*)(D->d_stage + sb.rg_off), prefix, G, boolean, seg)))
+  if ((rc = launch_rg_segtab(act.ctx, (const int64_t*)(D->d_stage + sb.rg_off), prefix, G, boolean, seg)))
     return fail_ctx(rc);
   *d_seg = seg;
   *nseg = G;
@@ -50,7 +50,7 @@ int orcg_reader::segments(Col& c, int slot, bool boolean, const uint64_t** d_seg
 
 bool orcg_reader::device_counts(uint32_t id) const {
   const Col& c = H->cols[id];
-  if (!rlev2_multi_capable(ctx->rlev2_variant)) return false;
+  if (!rlev2_multi_capable(act.ctx->rlev2_variant)) return false;
   if (c.kind == ORCG_TYPE_DECIMAL) return false;  // Decimal64V2's decode takes its count on the host
   // every per-row value stream is RLEv2 (a struct has none)
   for (const StreamDesc& d : layout(id, c))
@@ -60,10 +60,10 @@ bool orcg_reader::device_counts(uint32_t id) const {
 
 bool orcg_reader::device_work(uint32_t id) const {
   const Col& c = H->cols[id];
-  if (!selected[id] || !c.supported) return false;
+  if (!act.selected[id] || !c.supported) return false;
   if (c.s[kSlotPresent].present) return true;
   const uint32_t k = c.kind;
-  auto done = [&](int slot) { return !c.s[slot].present || batched.count((uint64_t)id * 8 + (uint64_t)slot) != 0; };
+  auto done = [&](int slot) { return !c.s[slot].present || B.find(id, slot) != nullptr; };
   if (k == ORCG_TYPE_STRUCT) {
     for (uint32_t st : footer.types[id].subtypes)
       if (device_work(st)) return true;
@@ -71,17 +71,16 @@ bool orcg_reader::device_work(uint32_t id) const {
   }
   if (is_int_kind(k)) return !done(kSlotData);
   if (k == ORCG_TYPE_DOUBLE) return false;  // the stream bytes are the values
-  if (k == ORCG_TYPE_DECIMAL && dec_done.count(id)) return false;  // the batch's decimal launch
-  if (is_string_kind(k) && is_dict(c.encoding)) return dict_done.count(id) == 0;
+  if (k == ORCG_TYPE_DECIMAL && B.dec_done.count(id)) return false;  // the batch's decimal launch
+  if (is_string_kind(k) && is_dict(c.encoding)) return B.dict_done.count(id) == 0;
   return true;
 }
 
 int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t** pout, const uint64_t* dcount) {
   const int slot = d.slot;
-  const uint64_t key = (uint64_t)(&c - H->cols.data()) * 8 + (uint64_t)slot;
-  const auto it = batched.find(key);
-  if (it != batched.end() && it->second.second == count) {
-    *pout = it->second.first;
+  const StripeBatch::Values* done = B.find((uint32_t)(&c - H->cols.data()), slot);
+  if (done && done->count == count) {
+    *pout = done->values;
     return ORCG_OK;
   }
   int64_t* out = alloc<int64_t>(count);
@@ -104,9 +103,9 @@ int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t
   const int sg = d.is_signed ? 1 : 0;
   madd(kMDecodeCall, 1);
   rc = timed(0, [&]() -> int {
-    if (v1) return launch_rlev1(ctx, d_src, sb.len, sg, d_seg, nseg, 0, count, out, 8);
-    return dcount ? launch_rlev2_tiled(ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8, dcount)
-                  : launch_rlev2(ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8);
+    if (v1) return launch_rlev1(act.ctx, d_src, sb.len, sg, d_seg, nseg, 0, count, out, 8);
+    return dcount ? launch_rlev2_tiled(act.ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8, dcount)
+                  : launch_rlev2(act.ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8);
   });
   return rc ? fail_ctx(rc) : ORCG_OK;
 }
@@ -131,7 +130,8 @@ int orcg_reader::byte_stream(Col& c, const StreamDesc& d, uint64_t count, uint8_
   if (rc) return rc;
   madd(kMByteCall, 1);
   rc = timed(1, [&]() -> int {
-    return launch_byterle(ctx, D->d_stage + sb.host_off, sb.len, d_seg, nseg, boolean, 0, count, out, d_ones, d_count);
+    return launch_byterle(act.ctx, D->d_stage + sb.host_off, sb.len, d_seg, nseg, boolean, 0, count, out, d_ones,
+                          d_count);
   });
   return rc ? fail_ctx(rc) : ORCG_OK;
 }

@@ -91,7 +91,7 @@ int orcg_reader::first_error(int inline_rc) {
   // host's inflate fails the stripe in prepare(), before any column decodes)
   if (F->inflate_word && F->h_rb[F->inflate_word] != kNoError) {
     const unsigned long long r = F->h_rb[F->inflate_word];
-    ctx->last_error_value = r >> 8;
+    act.ctx->last_error_value = r >> 8;
     return fail(dev_error_status((uint32_t)(r & 0xff)), dev_error_message((uint32_t)(r & 0xff)));
   }
   size_t ci = 0;
@@ -102,7 +102,7 @@ int orcg_reader::first_error(int inline_rc) {
     }
     if (rec[col] != kNoError) {
       const uint32_t code = (uint32_t)(rec[col] & 0xff);
-      ctx->last_error_value = rec[col] >> 8;
+      act.ctx->last_error_value = rec[col] >> 8;
       std::string m = dev_error_message(code);
       if (m == "unknown device error") {
         char b[96];
@@ -122,7 +122,7 @@ int orcg_reader::first_error(int inline_rc) {
   const unsigned long long own = F->h_rb[2 * nc];
   if (own != kNoError) {
     const uint32_t code = (uint32_t)(own & 0xff);
-    ctx->last_error_value = own >> 8;
+    act.ctx->last_error_value = own >> 8;
     return fail(dev_error_status(code), dev_error_message(code));
   }
   return ORCG_OK;
@@ -162,7 +162,7 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   // selected column (outputs and scratch); later stripes use what it took
   {
     size_t nsel = 0;
-    for (size_t i = 0; i < hs.cols.size(); ++i) nsel += selected[i] && hs.cols[i].supported ? 1 : 0;
+    for (size_t i = 0; i < hs.cols.size(); ++i) nsel += act.selected[i] && hs.cols[i].supported ? 1 : 0;
     ds.pool.hint = hs.used + hs.slack + hs.tail_bytes + 256 + 16 * nsel * footer.stripes[hs.stripe].num_rows + (1u << 20);
   }
   const size_t nc = hs.cols.size();
@@ -225,77 +225,42 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
     Ctx* c;
     unsigned long long* saved;
     ~OwnRecord() { c->d_err = saved; }
-  } own_rec{ctx, ctx->d_err};
-  ctx->d_err = (unsigned long long*)(ds.d_rb + 2 * nc);
-  batch.clear();
-  v1_segs.clear();
-  batched.clear();
-  dict_batch.clear();
-  dict_done.clear();
-  dict_pre.clear();
-  varint_jobs.clear();
-  varint_pre.clear();
-  dec_batch[0].clear();
-  dec_batch[1].clear();
-  dec_done.clear();
-  scan_jobs.clear();
-  scan_done.clear();
-  launches.clear();
+  } own_rec{act.ctx, act.ctx->d_err};
+  act.ctx->d_err = (unsigned long long*)(ds.d_rb + 2 * nc);
+  B.reset();
   const uint64_t nrows = nrows_stripe;
   const int64_t* rg_rows = hs.ngroups ? (const int64_t*)(ds.d_stage + hs.rows_off) : nullptr;
   // the batch: streams (and dictionaries) whose counts the host knows, their
   // job tables staged into the arena before the upload
   int rc = ORCG_OK;
   if (batch_on) {
-    ctx->arena_h = hs.h + arena_off;
-    ctx->arena_d = ds.d_stage + arena_off;
-    ctx->arena_cap = arena_cap;
-    ctx->arena_used = 0;
+    act.ctx->arena_h = hs.h + arena_off;
+    act.ctx->arena_d = ds.d_stage + arena_off;
+    act.ctx->arena_cap = arena_cap;
+    act.ctx->arena_used = 0;
     rc = collect(0, nrows, rg_rows);
-    if (!rc && !batch.empty() && (rc = plan_rlev2_multi(ctx, batch.data(), (uint32_t)batch.size(), launches)))
-      rc = fail_ctx(rc);
-    if (!rc && !v1_segs.empty() && (rc = plan_rlev1_multi(ctx, v1_segs.data(), v1_segs.size(), launches)))
-      rc = fail_ctx(rc);
-    if (!rc && !dict_batch.empty() &&
-        (rc = plan_dict_multi(ctx, dict_batch.data(), (uint32_t)dict_batch.size(), launches)))
-      rc = fail_ctx(rc);
-    for (int mode = 0; mode < 2 && !rc; ++mode) {
-      std::vector<DecJob>& g = dec_batch[mode];
-      if (g.empty()) continue;
-      uint64_t tiles = 0;
-      for (DecJob& j : g) {
-        j.tile0 = tiles;
-        tiles += (j.len + kVarintTile - 1) / kVarintTile;
-      }
-      const void* d = nullptr;
-      if ((rc = stage_table(ctx, g.data(), g.size() * sizeof(DecJob), &d))) {
-        rc = fail_ctx(rc);
-        break;
-      }
-      launches.push_back(MultiLaunch{5, mode, d, (uint32_t)g.size(), tiles, 0});
-    }
-    for (const ScanJob& j : scan_jobs) launches.push_back(MultiLaunch{6, 0, &j, 1, 0, 0});
-    ctx->arena_h = ctx->arena_d = nullptr;
-    ctx->arena_cap = 0;
+    if (!rc) rc = plan_batch();
+    act.ctx->arena_h = act.ctx->arena_d = nullptr;
+    act.ctx->arena_cap = 0;
   }
-  const uint64_t up = arena_off + ctx->arena_used;
+  const uint64_t up = arena_off + act.ctx->arena_used;
   stage_bytes += up;
   // (uploaded even after a failure above: finish() reads the records back);
   // a small stripe (configs[0]: ~60 KB) is pulled by a kernel from the
   // pinned staging, a large one copied by the DMA engine
   constexpr uint64_t pull_max = 256u << 10;
-  if (fl.ev_split && hipEventRecord(fl.ev_up0, ctx->stream) != hipSuccess) fl.ev_split = false;
+  if (fl.ev_split && hipEventRecord(fl.ev_up0, act.ctx->stream) != hipSuccess) fl.ev_split = false;
   const int urc = up <= pull_max && hs.pinned_mapped
-                      ? launch_pull(ctx, ds.d_stage, hs.h, up)
-                      : hip_check(ctx, hipMemcpyAsync(ds.d_stage, hs.h, up, hipMemcpyHostToDevice, ctx->stream),
+                      ? launch_pull(act.ctx, ds.d_stage, hs.h, up)
+                      : hip_check(act.ctx, hipMemcpyAsync(ds.d_stage, hs.h, up, hipMemcpyHostToDevice, act.ctx->stream),
                                   "H2D stripe");
   if (urc && !rc) rc = fail_ctx(urc);
-  if (fl.ev_split && hipEventRecord(fl.ev_up1, ctx->stream) != hipSuccess) fl.ev_split = false;
+  if (fl.ev_split && hipEventRecord(fl.ev_up1, act.ctx->stream) != hipSuccess) fl.ev_split = false;
   fl.t1 = now_s();
   // the stripe's Snappy chunks, ahead of every decode: compressed bytes and
   // the chunk table rode the upload, the streams land in the tail
   if (!rc && !hs.inflate.empty()) {
-    if ((rc = launch_snappy_inflate(ctx, ds.d_stage, (const orcg_snappy_chunk*)(ds.d_stage + hs.inflate_off),
+    if ((rc = launch_snappy_inflate(act.ctx, ds.d_stage, (const orcg_snappy_chunk*)(ds.d_stage + hs.inflate_off),
                                     hs.inflate.size(), ds.d_stage,
                                     (unsigned long long*)(ds.d_rb + fl.inflate_word))))
       rc = fail_ctx(rc);
@@ -306,43 +271,41 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   // configs[4]'s map keys): nothing reads its offsets before the fork's next
   // level, so it runs on side lane 0 beside the stripe's first decodes, not
   // ahead of them on the base stream (4 launches, ~45 us of a C5 stripe)
-  pre_on_lane = false;
   Ctx* pre_lane = nullptr;
-  if (!rc && !launches.empty() && batched.size() == dict_pre.size() && dict_done.empty() && scan_jobs.empty() &&
-      dec_batch[0].empty() && dec_batch[1].empty() && varint_jobs.empty() && side_lanes() > 1 &&
-      (ev_pre || hipEventCreateWithFlags(&ev_pre, hipEventDisableTiming) == hipSuccess))
-    pre_lane = ctx_lane(ctx, 0);
+  if (!rc && !B.launches.empty() && B.only_preloaded_dicts() && side_lanes() > 1 &&
+      (B.ev_pre || hipEventCreateWithFlags(&B.ev_pre, hipEventDisableTiming) == hipSuccess))
+    pre_lane = ctx_lane(act.ctx, 0);
   if (!rc && pre_lane) {
-    rc = hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "fork event");
-    if (!rc) rc = hip_check(ctx, hipStreamWaitEvent(pre_lane->stream, ctx->ev_fork, 0), "fork wait");
-    if (!rc && (rc = run_multi(pre_lane, launches))) ctx->last_error = pre_lane->last_error;
-    if (!rc) rc = hip_check(ctx, hipEventRecord(ev_pre, pre_lane->stream), "dictionary batch event");
+    rc = hip_check(act.ctx, hipEventRecord(act.ctx->ev_fork, act.ctx->stream), "fork event");
+    if (!rc) rc = hip_check(act.ctx, hipStreamWaitEvent(pre_lane->stream, act.ctx->ev_fork, 0), "fork wait");
+    if (!rc && (rc = run_multi(pre_lane, B.launches))) act.ctx->last_error = pre_lane->last_error;
+    if (!rc) rc = hip_check(act.ctx, hipEventRecord(B.ev_pre, pre_lane->stream), "dictionary batch event");
     if (rc) rc = fail_ctx(rc);
-    pre_on_lane = !rc;
-  } else if (!rc && !launches.empty() && (rc = timed(0, [&]() -> int { return run_multi(ctx, launches); }))) {
+    B.pre_on_lane = !rc;
+  } else if (!rc && !B.launches.empty() && (rc = timed(0, [&]() -> int { return run_multi(act.ctx, B.launches); }))) {
     rc = fail_ctx(rc);
   }
   if (!rc) rc = decode(0, nrows, nullptr, nrows, rg_rows);
-  if (pre_on_lane && hipStreamWaitEvent(ctx->stream, ev_pre, 0) != hipSuccess && !rc)
+  if (B.pre_on_lane && hipStreamWaitEvent(act.ctx->stream, B.ev_pre, 0) != hipSuccess && !rc)
     rc = fail(ORCG_DEVICE_ERROR, "dictionary batch wait failed");
-  batched_streams += batched.size();
+  batched_streams += B.batched.size();
   fl.rc = rc;
   fl.err_col = err_col;
   fl.err_msg = last_error;
-  if (fl.ev_split && hipEventRecord(fl.ev_dec, ctx->stream) != hipSuccess) fl.ev_split = false;
+  if (fl.ev_split && hipEventRecord(fl.ev_dec, act.ctx->stream) != hipSuccess) fl.ev_split = false;
   // the read-back copy, then the flight's event (queued copies land before
   // the buffers are reused)
-  if (hipMemcpyAsync(fl.h_rb, ds.d_rb, 8 * fl.rb_used, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-      hipEventRecord(fl.done, ctx->stream) != hipSuccess) {
+  if (hipMemcpyAsync(fl.h_rb, ds.d_rb, 8 * fl.rb_used, hipMemcpyDeviceToHost, act.ctx->stream) != hipSuccess ||
+      hipEventRecord(fl.done, act.ctx->stream) != hipSuccess) {
     (void)hipGetLastError();
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(act.ctx->stream);
     if (!fl.rc) {
       fl.rc = ORCG_DEVICE_ERROR;
       fl.err_msg = "read error records";
     }
     // (the records are unreadable: finish() reports fl.rc)
     memset(fl.h_rb, 0xff, 8 * fl.rb_used);
-    (void)hipEventRecord(fl.done, ctx->stream);
+    (void)hipEventRecord(fl.done, act.ctx->stream);
   }
   fl.enqueued = true;
   H = nullptr;
@@ -410,10 +373,10 @@ int orcg_reader::upload_and_decode(HostStage& hs, DevSlot& ds) {
 // finished. One thread for the whole read: a thread per stripe cost more
 // than a configs[0] stripe decodes in.
 int orcg_reader::read_stripes(uint64_t first, uint64_t count) {
-  if (!ctx) return fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
+  if (!act.ctx) return fail(ORCG_INVALID_ARGUMENT, "reader has no device context");
   if (first > footer.stripes.size() || count > footer.stripes.size() - first)
     return fail(ORCG_INVALID_ARGUMENT, "stripe index out of range");
-  hipSetDevice(ctx->device);
+  hipSetDevice(act.ctx->device);
   for (auto& t : timings) t = 0;
   stream_stats[0] = stream_stats[1] = 0;
   batched_streams = 0;
@@ -433,7 +396,7 @@ int orcg_reader::read_stripes(uint64_t first, uint64_t count) {
         pcv.wait(lk, [&] { return quit || k < released + 3; });  // stripe k - 3 released stages[k % 3]
         if (quit) return;
       }
-      prepare(first + k, stages[k % 3]);
+      prepare(first + k, stages[k % 3], act);
       {
         std::lock_guard<std::mutex> lk(pm);
         prepared = k + 1;

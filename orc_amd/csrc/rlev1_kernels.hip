@@ -715,7 +715,7 @@ int plan_rlev1_multi(Ctx* ctx, const V1SegDesc* segs, uint64_t nsegs, std::vecto
     const void* d = nullptr;
     const int rc = stage_table(ctx, v.data(), v.size() * sizeof(V1SegDesc), &d);
     if (rc) return rc;
-    out.push_back(MultiLaunch{1, w == 0 ? 4 : 16, d, 0, v.size(), 0});
+    out.push_back(MultiLaunch{MultiLaunch::kRlev1, w == 0 ? 4 : 16, d, 0, v.size(), 0});
   }
   return ORCG_OK;
 }

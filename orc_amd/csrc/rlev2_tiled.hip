@@ -2236,7 +2236,7 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     // only segment-table jobs for these variants, rlev2_multi_capable)
     for (uint32_t j = 0; j < njobs; ++j) {
       if (!jobs[j].segtab) return set_error(ctx, ORCG_INVALID_ARGUMENT, "row-index job needs a multi-stream instance");
-      out.push_back(MultiLaunch{3, pinned, jobs + j, 1, jobs[j].nsegs, jobs[j].nvalues});
+      out.push_back(MultiLaunch{MultiLaunch::kRlev2Pinned, pinned, jobs + j, 1, jobs[j].nsegs, jobs[j].nvalues});
     }
     return ORCG_OK;
   }
@@ -2277,7 +2277,7 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     const int rc = stage_rle_jobs(ctx, g.data(), (uint32_t)g.size(), &d);
     if (rc) return rc;
     const int lv = (v == 6 && !pinned) ? union_variant(ctx, segs) : v;
-    MultiLaunch m{0, lv, d, (uint32_t)g.size(), segs, values};
+    MultiLaunch m{MultiLaunch::kRlev2, lv, d, (uint32_t)g.size(), segs, values};
     if (lv == 6 && entries < 0xffff0000ull) {
       m.tab_entries = entries;
       two_pass_shape(bound, &m.spg, &m.slice);

@@ -82,14 +82,12 @@ static void col_set(ColOut& o, int f, const void* p) {
 
 struct orcg_row_reader {
   orcg_reader* r = nullptr;
-  // this row reader's RowReaderOptions
-  std::vector<uint8_t> selected;
-  bool lazy_dict = false;
-  const ZoneEntry* reader_tz = nullptr;  // setTimezoneName (nullptr: GMT)
-  std::string local_tz;                  // the zone of stripes that name none
-  std::shared_ptr<const ReadPlan> read;  // setReadType: the reader's at creation
-  bool evo_throw = false;                // throwOnSchemaEvolutionOverflow, likewise
-  bool dev_inflate = false;              // orcg_reader_set_device_decompression, likewise
+  // This row reader's options: the reader's at its creation, with the
+  // RowReaderOptions it was created with on top; immutable from then on.
+  // opt.ctx is the worker's own context (stream, error record, scratch,
+  // queues), owned here: the caller's context may be driven by its thread
+  // while the worker decodes ahead, e.g. by another reader sharing it
+  ReadOptions opt;
   uint64_t nstripes = 0, first = 0, last = 0;  // stripes [first, last) are in range
   uint64_t current = 0, row_in_stripe = 0, rows_in_stripe = 0;
   uint64_t previous_row = 0;
@@ -124,10 +122,6 @@ struct orcg_row_reader {
   // helpers are placed there too, GpuRowReader.hh CopyPool)
   int node = -1;
   void addp(int i, double sec) { prof[i].fetch_add((uint64_t)(sec * 1e9), std::memory_order_relaxed); }
-  // the worker's own context (stream, error record, scratch, queues): the
-  // caller's context may be driven by its thread while the worker decodes
-  // ahead, e.g. by another reader sharing it
-  orcg_ctx* own = nullptr;
 
   ~orcg_row_reader() {
     {
@@ -137,7 +131,7 @@ struct orcg_row_reader {
     }
     cv.notify_all();
     if (worker.joinable()) worker.join();
-    if (own) orcg_ctx_destroy(own);
+    if (opt.ctx) orcg_ctx_destroy(static_cast<orcg_ctx*>(opt.ctx));
   }
 
   void mark_end_of_file() {
@@ -218,15 +212,15 @@ struct orcg_row_reader {
     last_d2h = 0;
     for (const Range& rg : rs) last_d2h += rg.bytes;
     for (const Range& rg : rs) {
-      const int rc = hip_check(r->ctx, hipMemcpyAsync(sl.h + rg.hoff, rg.d, rg.bytes, hipMemcpyDeviceToHost,
-                                                      r->ctx->stream), "D2H row batch");
+      const int rc = hip_check(opt.ctx, hipMemcpyAsync(sl.h + rg.hoff, rg.d, rg.bytes, hipMemcpyDeviceToHost,
+                                                       opt.ctx->stream), "D2H row batch");
       if (rc) return r->fail_ctx(rc);
     }
     for (const Buf& bf : bufs) {  // the slab's views point at host memory
       const Range& rg = rs[bf.range];
       col_set(sl.out[bf.col], bf.f, sl.h + rg.hoff + (uint64_t)(bf.d - rg.d));
     }
-    const int rc = hip_check(r->ctx, hipStreamSynchronize(r->ctx->stream), "hipStreamSynchronize");
+    const int rc = hip_check(opt.ctx, hipStreamSynchronize(opt.ctx->stream), "hipStreamSynchronize");
     return rc ? r->fail_ctx(rc) : ORCG_OK;
   }
   void run_job(uint64_t t) {
@@ -248,7 +242,7 @@ struct orcg_row_reader {
         prepared[u & 1] = u;
         ahead = std::thread([this, u] {
           const double tp = now_s();
-          (void)r->prepare(u, stage[u & 1], selected, local_tz, dev_inflate);  // a failure is kept in the stage
+          (void)r->prepare(u, stage[u & 1], opt);  // a failure is kept in the stage
           addp(4, now_s() - tp);
         });
       }
@@ -256,12 +250,12 @@ struct orcg_row_reader {
     if (prepared[t & 1] == t) start_ahead();
     {
       std::lock_guard<std::mutex> lk(r->mu);
-      orcg_reader::Active act(r, own, selected, lazy_dict, reader_tz, local_tz, read, evo_throw, dev_inflate);
-      (void)hipSetDevice(r->ctx->device);
+      orcg_reader::Active scope(r, opt);
+      (void)hipSetDevice(opt.ctx->device);
       rc = ORCG_OK;
       if (prepared[t & 1] != t) {
         prepared[t & 1] = t;
-        rc = r->prepare(t, hs);
+        rc = r->prepare(t, hs, opt);
         start_ahead();
       } else {
         rc = hs.rc;
@@ -381,40 +375,39 @@ extern "C" {
 int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* o, orcg_row_reader** out) {
   if (!r || !out) return ORCG_INVALID_ARGUMENT;
   *out = nullptr;
-  if (!r->own_ctx) return r->fail_user(ORCG_INVALID_ARGUMENT, "reader has no device context");
+  if (!r->own.ctx) return r->fail_user(ORCG_INVALID_ARGUMENT, "reader has no device context");
   const uint64_t off = o ? o->offset : 0;
   const uint64_t len = o ? o->length : ~0ull;
   std::unique_ptr<orcg_row_reader> rr(new orcg_row_reader());
   rr->r = r;
-  int rc = compute_selection(r, o ? o->include : nullptr, o && o->include ? o->include_len : 0, rr->selected);
-  if (rc) return rc;
-  rr->lazy_dict = o && o->lazy_dictionary != 0;
   {
-    // its own copy of the reader's zones; opts->timezone replaces the reader zone
+    // the reader's options as they are now
     std::lock_guard<std::mutex> lk(r->mu);
-    rr->reader_tz = r->own_reader_tz;
-    rr->local_tz = r->own_local_tz;
-    // and of its read type and overflow rule
-    rr->read = r->own_read;
-    rr->evo_throw = r->own_evo_throw;
-    rr->dev_inflate = r->own_dev_inflate;
+    rr->opt = r->own;
   }
+  rr->opt.ctx = nullptr;  // its own, created below
+  // then its RowReaderOptions: include, lazy decoding; opts->timezone replaces the reader zone
+  int rc = compute_selection(r, o ? o->include : nullptr, o && o->include ? o->include_len : 0, rr->opt.selected);
+  if (rc) return rc;
+  rr->opt.lazy_dict = o && o->lazy_dictionary != 0;
   if (o && o->timezone) {
     const ZoneEntry* z = r->resolve_zone(o->timezone);
     if (!z || !z->zone)
       return r->fail_user(z ? ORCG_PARSE_ERROR : ORCG_INVALID_ARGUMENT,
                           z ? z->err : std::string("Time zone ") + o->timezone + " not found");
-    rr->reader_tz = z;
+    rr->opt.reader_tz = z;
   }
   rr->node = current_numa_node();
-  if ((rc = orcg_ctx_create(r->own_ctx->device, &rr->own)) != ORCG_OK)
+  orcg_ctx* own = nullptr;
+  if ((rc = orcg_ctx_create(r->own.ctx->device, &own)) != ORCG_OK)
     return r->fail_user(rc, "row reader context creation failed");
+  rr->opt.ctx = own;
   // the caller's kernel choice, snapshotted once: the worker never reads the
   // caller's context
-  rr->own->rlev2_variant = r->own_ctx->rlev2_variant;
+  own->rlev2_variant = r->own.ctx->rlev2_variant;
   // its side lanes (streams, events, error records) now, not in the first
   // stripe's decode
-  if (side_lanes() > 1) (void)ctx_lane(rr->own, side_lanes() - 1);
+  if (side_lanes() > 1) (void)ctx_lane(own, side_lanes() - 1);
   const uint64_t ns = r->footer.stripes.size();
   rr->nstripes = ns;
   rr->current = ns;
@@ -453,7 +446,7 @@ int orcg_row_reader_create(orcg_reader* r, const orcg_row_reader_options* o, orc
 void orcg_row_reader_destroy(orcg_row_reader* rr) { delete rr; }
 
 int orcg_row_reader_is_selected(const orcg_row_reader* rr, uint32_t type_id) {
-  return rr && type_id < rr->selected.size() && rr->selected[type_id] ? 1 : 0;
+  return rr && type_id < rr->opt.selected.size() && rr->opt.selected[type_id] ? 1 : 0;
 }
 
 int orcg_row_reader_next(orcg_row_reader* rr, uint64_t capacity, uint64_t* rows) {

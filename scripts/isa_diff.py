@@ -8,7 +8,9 @@ REV_B defaults to the working tree. For each side, orc_amd/csrc and include/
 are materialised in a temporary directory and the unit is compiled with
 orc_amd/build.py's flags plus `--cuda-device-only -S` (and the -D flags). The
 two assembly files are cut into one piece per function (a kernel's piece
-holds its code and its .amdhsa_* resource directives), paired by name and
+holds its code and its .amdhsa_* resource directives) and per data object
+(the compiler does not keep two device globals in one order from run to run),
+paired by name and
 compared as text after normalising the `__hip_cuid_<hash>` symbol, which
 hashes the source, and the function ordinals in local labels; a function on
 one side only is listed.
@@ -61,12 +63,12 @@ def compile_asm(rev, tu, defines, workdir):
         return f.read()
 
 
-FUNC = re.compile(r"^\s*\.type\s+(\S+),@function")
+FUNC = re.compile(r"^\s*\.type\s+(\S+),@(?:function|object)")
 HEAD = re.compile(r"^\s*\.(section|text|globl|protected|hidden|weak|p2align)\b")
 
 
 def pieces(text, by_order):
-    """[(name, [lines])]: a preamble, one piece per function, the metadata."""
+    """[(name, [lines])]: a preamble, one piece per function or object, the metadata."""
     text = re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid_", text)
     # local labels carry their function's ordinal (.LBB12_3, .Lfunc_end12):
     # dropped, so that a function compares equal wherever it stands in the unit

@@ -8,6 +8,9 @@ other capacities (batches never exceed the capacity nor span a stripe:
 RowReaderImpl::next, c++/src/Reader.cc:1392-1442), seekToRow at row-group
 and stripe edges (:428-499), range(offset, length) stripe selection
 (:337-345) and lazy dictionary decoding (nextEncoded, ColumnReader.cc:596-607).
+Last, the rule that a row reader keeps every option of its creation, on a
+Snappy file written at test time whose TIMESTAMP column has a writer zone
+other than UTC.
 """
 import os
 
@@ -15,8 +18,11 @@ import numpy as np
 import pytest
 
 import orc_amd
-from conftest import load_golden
-from file_parity import expected_json, path, printer_equal, to_printer_form
+import snappy_model
+import tz_model
+from conftest import GOLDEN, load_golden
+from file_parity import expected_json, first_difference, path, printer_equal, to_printer_form
+from orc_craft import field_bytes, field_varint
 
 pytestmark = pytest.mark.gpu
 
@@ -299,3 +305,201 @@ def test_row_indexed_file_under_every_variant(ctx, name):
                 assert r.read_stripe(s).to_pylist() == base[s], "variant %d stripe %d" % (v, s)
     finally:
         ctx.set_rlev2_variant(0)
+
+
+# ---- a row reader keeps every option of its creation ------------------------
+
+TZ = os.path.join(GOLDEN, "tz")
+WRITER_ZONE, OTHER_ZONE = "America/Los_Angeles", "Asia/Shanghai"
+OPT_ROWS, OPT_STRIPE = 4000, 2000
+
+
+def _fields(buf):
+    """[(field, wire type, value)] of a message of varint and bytes fields."""
+    out, p = [], 0
+
+    def vint():
+        nonlocal p
+        v = sh = 0
+        while True:
+            b = buf[p]
+            p += 1
+            v |= (b & 0x7F) << sh
+            sh += 7
+            if not b & 0x80:
+                return v
+    while p < len(buf):
+        key = vint()
+        assert key & 7 in (0, 2), "wire type %d" % (key & 7)
+        if key & 7 == 0:
+            out.append((key >> 3, 0, vint()))
+        else:
+            n = vint()
+            out.append((key >> 3, 2, bytes(buf[p:p + n])))
+            p += n
+    return out
+
+
+def _message(fields):
+    return b"".join(field_varint(f, v) if w == 0 else field_bytes(f, v) for f, w, v in fields)
+
+
+def _stored(body):
+    """One stored ("original") compression chunk."""
+    return (len(body) << 1 | 1).to_bytes(3, "little") + body
+
+
+def with_writer_zone(data, zone):
+    """The Snappy file `data` with every StripeFooter.writerTimezone replaced
+    (pyarrow's writer knows GMT only): the stripe footers and the file footer
+    are rewritten as stored chunks, the stripes' offsets and footer lengths,
+    the content length and the PostScript's footer length follow."""
+    def get(m, f):
+        return [v for g, _, v in m if g == f]
+    ps_len = data[-1]
+    ps = _fields(data[-1 - ps_len:-1])
+    foot_len, block, meta_len = get(ps, 1)[0], get(ps, 3)[0], (get(ps, 5) or [0])[0]
+    foot_at = len(data) - 1 - ps_len - foot_len
+    foot, err = snappy_model.decode_framed(data[foot_at:foot_at + foot_len], block)
+    assert err is None
+    foot = _fields(foot)
+    body, src, stripes = bytearray(data[:3]), 3, []
+    for s in get(foot, 3):
+        s = _fields(s)
+        off, ilen, dlen, flen = (get(s, f)[0] for f in (1, 2, 3, 4))
+        assert off == src, "the stripes are contiguous"
+        sf, err = snappy_model.decode_framed(data[off + ilen + dlen:off + ilen + dlen + flen], block)
+        assert err is None
+        sf = _stored(_message([(f, w, zone.encode() if f == 3 else v) for f, w, v in _fields(sf)]))
+        stripes.append(_message([(f, w, {1: len(body), 4: len(sf)}.get(f, v)) for f, w, v in s]))
+        body += data[off:off + ilen + dlen] + sf
+        src = off + ilen + dlen + flen
+    assert src == foot_at - meta_len
+    body += data[src:foot_at]  # the metadata section
+    it = iter(stripes)
+    foot = _stored(_message([(f, w, len(body) - meta_len if f == 2 else next(it) if f == 3 else v)
+                             for f, w, v in foot]))
+    ps = _message([(f, w, len(foot) if f == 1 else v) for f, w, v in ps])
+    return bytes(body) + foot + ps + bytes([len(ps)])
+
+
+def _zone(name):
+    with open(os.path.join(TZ, name), "rb") as f:
+        return f.read()
+
+
+def _open_with_zones(p, ctx):
+    r = orc_amd.Reader(p, ctx)
+    for name in (WRITER_ZONE, OTHER_ZONE, "GMT"):
+        r.set_zone_rules(name, _zone(name))  # never the machine's tzdata
+    return r
+
+
+@pytest.fixture(scope="module")
+def options_file(tmp_path_factory):
+    """struct<id:bigint,s:string,ts:timestamp>, Snappy, two stripes of 2,000
+    rows: ids that fit an int, 16 distinct strings (dictionary encoded), wall
+    clocks across both 2023 US transitions written in America/Los_Angeles.
+    Returns (path, rows as read in GMT, rows as read in Asia/Shanghai), the
+    timestamps by tests/tz_model.py."""
+    import pyarrow as pa
+    import pyarrow.orc as po
+    os.environ.setdefault("TZDIR", TZ)  # the ORC writer looks its zone (GMT) up
+    rng = np.random.default_rng(5)
+    ids = rng.integers(-(1 << 31), 1 << 31, OPT_ROWS, dtype=np.int64)
+    words = ["word-%02d" % i for i in range(16)]
+    strs = [words[int(k)] for k in rng.integers(0, 16, OPT_ROWS)]
+    secs = np.concatenate([np.arange(e - 1000, e + 1000) for e in (1678586400, 1699146000)])
+    nanos = rng.integers(0, 1_000_000_000, OPT_ROWS)
+    t = pa.table({"id": pa.array(ids), "s": pa.array(strs),
+                  "ts": pa.array(secs * 1_000_000_000 + nanos, pa.timestamp("ns"))})
+    d = tmp_path_factory.mktemp("options")
+    po.write_table(t, str(d / "gmt.orc"), compression="snappy", compression_block_size=65536, stripe_size=1,
+                   batch_size=OPT_STRIPE, dictionary_key_size_threshold=0.5)
+    p = str(d / "los_angeles.orc")
+    with open(str(d / "gmt.orc"), "rb") as f:
+        data = with_writer_zone(f.read(), WRITER_ZONE)
+    with open(p, "wb") as f:
+        f.write(data)
+    # pyarrow reads the rewritten file; not its ts column, for which it would
+    # look the writer zone up under whatever $TZDIR is by now
+    f = po.ORCFile(p)
+    assert [f.read_stripe(s, columns=["id"]).num_rows for s in range(f.nstripes)] == [OPT_STRIPE] * 2
+    assert f.compression == "SNAPPY"
+    assert f.read(columns=["id", "s"]).equals(t.select(["id", "s"]))
+    # the stream values are the GMT writer's: read as the writer zone's, then in the reader zone
+    la = tz_model.Zone(WRITER_ZONE, _zone(WRITER_ZONE))
+    rows = {}
+    for name in ("GMT", OTHER_ZONE):
+        z = tz_model.Zone(name, _zone(name))
+        ts = [tz_model.convert(la, z, int(v) - tz_model.ORC_EPOCH_UTC + la.epoch) for v in secs]
+        rows[name] = [{"id": int(i), "s": w, "ts": np.datetime64(int(x) * 1_000_000_000 + int(n), "ns")}
+                      for i, w, x, n in zip(ids, strs, ts, nanos)]
+    return p, rows["GMT"], rows[OTHER_ZONE]
+
+
+def _drain(rr, capacity=512):
+    b = rr.create_row_batch(capacity)
+    rows = []
+    while rr.next(b):
+        rows += b.to_pylist()
+    return rows
+
+
+def test_a_row_reader_keeps_every_option_of_its_creation(ctx, options_file):
+    """Row reader A is created, then every option of the reader changes (the
+    selection, lazy dictionaries, the reader zone, the read type with throwing
+    overflow, device decompression), row reader B is created and the options
+    are put back. A and B read interleaved, a batch each in turn, across a
+    stripe edge and batch edges: A gives the reader's rows of before the
+    change, B those of a reader that had B's options from the start, and the
+    reader's own read afterwards equals its first. The Snappy chunks inflated
+    on the device are exactly B's."""
+    import test_gpu_snappy_files as snappy_files
+    p, want_gmt, want_other = options_file
+    with open(p, "rb") as f:
+        b_chunks, b_bytes = snappy_files.expected_inflate(f.read())
+    assert b_chunks > 0
+    read_type = "struct<id:int,s:string,ts:timestamp>"
+    r = _open_with_zones(p, ctx)
+    first = r.read()
+    assert first_difference(want_gmt, first) is None
+    a = r.create_row_reader()
+    r.select([1])
+    r.set_lazy_dictionary(True)
+    r.set_timezone(OTHER_ZONE)
+    r.set_read_type(read_type, throw_on_overflow=True)
+    r.set_device_decompression(True)
+    assert r.last_device_inflate() == (0, 0)  # whatever A's worker has decoded by now
+    b = r.create_row_reader()
+    r.select(None)
+    r.set_lazy_dictionary(False)
+    r.set_timezone("GMT")
+    r.set_read_type(None, throw_on_overflow=False)
+    r.set_device_decompression(False)
+    ba, bb = a.create_row_batch(512), b.create_row_batch(512)
+    rows_a, rows_b = [], []
+    more_a = more_b = True
+    while more_a or more_b:
+        if more_a:
+            more_a = a.next(ba)
+            if more_a:
+                assert ba.types[1].kind == 4 and ba.columns[2].data is not None  # bigint, strings resolved
+                rows_a += ba.to_pylist()
+        if more_b:
+            more_b = b.next(bb)
+            if more_b:
+                assert bb.types[1].kind == 3 and set(bb.columns) == {0, 1, 2, 3}  # int; its own selection
+                rows_b += bb.to_pylist()
+    # every stripe of both is decoded: the reader's counter holds B's chunks and none of A's
+    assert r.last_device_inflate() == (b_chunks, b_bytes)
+    assert first_difference(first, rows_a) is None
+    assert first_difference(want_other, rows_b) is None
+    once = _open_with_zones(p, ctx)
+    once.set_timezone(OTHER_ZONE)
+    once.set_read_type(read_type, throw_on_overflow=True)
+    once.set_device_decompression(True)
+    assert first_difference(_drain(once.create_row_reader()), rows_b) is None
+    last = r.read()
+    assert r.last_device_inflate() == (0, 0)
+    assert first_difference(first, last) is None
