@@ -508,6 +508,34 @@ int orcg_snappy_plan(const uint8_t* src, uint64_t len, uint64_t block_size, orcg
 int orcg_snappy_decompress_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src_len,
                                   const orcg_snappy_chunk* table, uint64_t nchunks, uint8_t* d_dst, uint64_t dst_len);
 
+/* ---- LZ4 chunks inflated on the device ------------------------------------
+ * The same for LZ4 (raw blocks, the codec of ORC's LZ4 files). A block does
+ * not state its decompressed length: the plan walks its sequence tokens
+ * (copying nothing) and runs every check of the block there, so a corrupt
+ * block fails the plan. The rules are the format's safety rules: a literal
+ * lies inside the input and the output, an offset is neither 0 nor past the
+ * output so far, a match ends inside the output, the block ends with a literal
+ * run. They accept every block a writer produces. liblz4, which the host path
+ * calls, differs on crafted blocks in two ways: it may accept a zero offset,
+ * and it refuses blocks that break its compressor's end-of-block margins. The
+ * table entry is Snappy's; dst_bytes is the walked size. */
+#define ORCG_LZ4_STORED 1u
+typedef orcg_snappy_chunk orcg_lz4_chunk;
+
+/* out[0] = bytes of decompressed history a chunk keeps on chip (every LZ4
+ * offset lies inside it), out[1] = threads per chunk. */
+void orcg_lz4_device_info(uint32_t out[2]);
+/* As orcg_snappy_plan. The one text of a failing block is "Corrupt lz4
+ * compressed block", also when it inflates past min(block_size, 2^31 - 1). */
+int orcg_lz4_plan(const uint8_t* src, uint64_t len, uint64_t block_size, orcg_lz4_chunk* table, uint64_t cap,
+                  uint64_t* nchunks, uint64_t* total, const char** error);
+/* As orcg_snappy_decompress_device. The kernel repeats every check of the
+ * plan (the table is not trusted) and that a block ends at dst_bytes exactly:
+ * ORCG_PARSE_ERROR "Corrupt lz4 compressed block", orcg_ctx_last_error_value
+ * = the lowest failing chunk's index. */
+int orcg_lz4_decompress_device(orcg_ctx* ctx, const uint8_t* d_src, uint64_t src_len, const orcg_lz4_chunk* table,
+                               uint64_t nchunks, uint8_t* d_dst, uint64_t dst_len);
+
 /* (Roofline calibration copies, orcg_probe_copy, live only in the A/B build
  * liborcgpu_ab.so: orc_amd/csrc/probe_kernels.hip.) */
 

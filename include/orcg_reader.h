@@ -156,17 +156,23 @@ int orcg_reader_is_selected(const orcg_reader* r, uint32_t type_id);
 /* RowReaderOptions::setEnableLazyDecoding: dictionary string columns decode to
  * index + dictionary only (StringDictionaryColumnReader::nextEncoded). */
 int orcg_reader_set_lazy_dictionary(orcg_reader* r, int on);
-/* Device decompression (off by default): with it on, a Snappy file's chunks of
- * the streams the host never walks -- DATA of DIRECT-encoded string / varchar
- * / char / binary columns, DICTIONARY_DATA, DATA of float / double, DATA of
- * varint decimals -- are uploaded compressed and inflated by one launch per
- * stripe ahead of its decodes (orcg_snappy_decompress_device's kernel). Every
- * other stream (RLE and byte-RLE streams, PRESENT, LENGTH, SECONDARY,
- * ROW_INDEX) is inflated on the host as before, and so is every stream of a
- * file with another codec. Results and errors are the same either way: a
- * corrupt preamble fails the stripe's preparation, a corrupt chunk body fails
- * the stripe with ORCG_PARSE_ERROR and the host decoder's text, ahead of any
- * column's error. Row readers created afterwards take the setting with them. */
+/* Device decompression (off by default): with it on, a Snappy or LZ4 file's
+ * chunks of the streams the host never walks -- DATA of DIRECT-encoded string
+ * / varchar / char / binary columns, DICTIONARY_DATA, DATA of float / double,
+ * DATA of varint decimals -- are uploaded compressed and inflated by one
+ * launch per stripe ahead of its decodes (orcg_snappy_decompress_device's or
+ * orcg_lz4_decompress_device's kernel). Every other stream (RLE and byte-RLE
+ * streams, PRESENT, LENGTH, SECONDARY, ROW_INDEX) is inflated on the host as
+ * before, and so is every stream of a zlib, zstd or LZO file. Results and
+ * errors are the same either way: a corrupt Snappy preamble fails the
+ * stripe's preparation, a corrupt Snappy chunk body fails the stripe with
+ * ORCG_PARSE_ERROR and the host decoder's text, ahead of any column's error.
+ * An LZ4 block states no length: the preparation walks its tokens for it and
+ * runs every check there, so a corrupt LZ4 block fails the preparation with
+ * "Corrupt lz4 compressed block", as with the setting off. (On crafted LZ4
+ * blocks the walk and liblz4 differ in the two ways orcg.h "LZ4 chunks"
+ * names; on what a writer produces they agree.) Row readers created
+ * afterwards take the setting with them. */
 int orcg_reader_set_device_decompression(orcg_reader* r, int on);
 /* out[0] = chunks, out[1] = decompressed bytes the last read inflated on the
  * device, summed over its stripes (0, 0 with the setting off). ReaderMetrics'

@@ -41,6 +41,7 @@ from .rle import (  # noqa: F401
     timestamp_decode_tz_device,
 )
 from .snappy import snappy_decompress_device, snappy_device_info, snappy_plan  # noqa: F401,E402
+from .lz4 import lz4_decompress_device, lz4_device_info, lz4_plan  # noqa: F401,E402
 from .timezone import Timezone  # noqa: F401,E402
 
 from .reader import Reader, RowReader, UnionValue, open_reader  # noqa: F401,E402

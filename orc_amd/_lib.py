@@ -127,6 +127,9 @@ SIGNATURES = [
     ("orcg_snappy_device_info", [ctypes.POINTER(ctypes.c_uint32)], None),
     ("orcg_snappy_plan", [vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(cp)], i32),
     ("orcg_snappy_decompress_device", [vp, vp, u64, vp, u64, vp, u64], i32),
+    ("orcg_lz4_device_info", [ctypes.POINTER(ctypes.c_uint32)], None),
+    ("orcg_lz4_plan", [vp, u64, u64, vp, u64, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(cp)], i32),
+    ("orcg_lz4_decompress_device", [vp, vp, u64, vp, u64, vp, u64], i32),
 ]
 
 # symbols of the A/B build (liborcgpu_ab.so, ORCG_LIB) only

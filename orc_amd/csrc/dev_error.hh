@@ -34,6 +34,8 @@ enum DevErr : uint32_t {
   kErrSnappyCopyTruncated = 16,
   kErrSnappyCopyRange = 17,
   kErrSnappyLength = 18,
+  // LZ4 chunks inflated on the device: the host path's one text (decompress_chunk, orc_file.cpp)
+  kErrLz4 = 19,
 };
 
 inline const char* dev_error_message(uint32_t code) {
@@ -58,6 +60,7 @@ inline const char* dev_error_message(uint32_t code) {
     case kErrSnappyCopyTruncated: return "snappy: truncated copy";
     case kErrSnappyCopyRange: return "snappy: copy out of range";
     case kErrSnappyLength: return "snappy: length mismatch";
+    case kErrLz4: return "Corrupt lz4 compressed block";
   }
   return "unknown device error";
 }

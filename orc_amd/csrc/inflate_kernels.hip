@@ -1,6 +1,8 @@
 // Snappy (raw block format) decompression of independent chunks on the device:
 // the device half of the host's snappy_decompress (orc_file.cpp), with its
 // check order and texts (dev_error.hh kErrSnappy*). DESIGN.md §3.11.
+// LZ4 (raw blocks) on the same ring, slice and flush:
+// lz4_inflate_kernel below.
 //
 // One wavefront owns one chunk. The decompressed history lives in an LDS ring
 // of kSnappyRing bytes: a copy element reads what the elements before it
@@ -92,7 +94,169 @@ __device__ __forceinline__ uint32_t flush(const uint8_t* ring, uint8_t* out, uin
   return f;
 }
 
+// LZ4's literal piece: source bytes [p, p + piece) -> the ring bytes of output
+// [o, o + piece). Lane l takes source bytes [4l, 4l + 4) of each 256. A copy
+// of the loop in snappy_inflate_kernel: called from there, it changed that
+// kernel's instruction schedule (DESIGN.md §3.1 has the same with stream_desc).
+__device__ __forceinline__ void lz4_literal_piece(const ChunkSrc& c, uint8_t* ring, uint32_t align, uint32_t p,
+                                                  uint32_t o, uint32_t piece, int lane) {
+  for (uint32_t k = 4u * lane; k < piece; k += 4u * kWave) {
+    const uint32_t a = c.adj + p + k;
+    const uint32_t w0 = __builtin_amdgcn_raw_buffer_load_b32(c.rs, a & ~3u, 0, 0);
+    const uint32_t w1 = __builtin_amdgcn_raw_buffer_load_b32(c.rs, (a & ~3u) + 4u, 0, 0);
+    const uint32_t w = (uint32_t)((((uint64_t)w1 << 32) | w0) >> ((a & 3u) * 8));
+    const uint32_t r = align + o + k;
+    if (k + 4 <= piece && (r & 3u) == 0) {
+      *(uint32_t*)(ring + (r & kMask)) = w;
+    } else {
+      for (uint32_t j = 0; j < 4 && k + j < piece; ++j) ring[(r + j) & kMask] = (uint8_t)(w >> (8 * j));
+    }
+  }
+  asm volatile("" ::: "memory");
+}
+
+// LZ4: a match is expanded in steps of kStep bytes, a byte a lane
+constexpr uint32_t kStep = kWave;
+// the unflushed bytes (< kFlush between steps and pieces) must survive the
+// next piece or step; writing output byte x takes the ring byte of x - kRing,
+// which no later offset (<= 65,535 < kRing) reaches
+static_assert(kLz4Ring == kRing && kLz4Threads == kWave, "one ring, one wavefront");
+static_assert(kFlush + kPiece <= kRing && kFlush + kStep <= kRing,
+              "the ring holds the unflushed bytes and the next piece or step");
+static_assert(65535 < kRing, "every LZ4 offset lies inside the ring");
+
+// The extension bytes of a length (15 in the token): bytes are added until
+// one is not 255. False: the chunk ends inside the run, or the length passed
+// `room` (what can still fit; len < 2^31 + 255, no wrap). The run may be
+// longer than the slice: peek reloads inside it.
+__device__ __forceinline__ bool lz4_extend(const ChunkSrc& c, Slice& s, uint32_t& p, uint32_t n, uint32_t& len,
+                                           uint32_t room, int lane) {
+  for (;;) {
+    if (p >= n) return false;
+    const uint32_t b = (uint32_t)peek(c, s, p, lane) & 0xffu;
+    ++p;
+    len += b;
+    if (len > room) return false;
+    if (b != 255u) return true;
+  }
+}
+
 }  // namespace
+
+// LZ4 raw blocks: lz4_block_size's rules (inflate_plan.hh), each repeated ahead
+// of the store it guards, one code. ulen = the table's dst_bytes plays the
+// walk's cap, and the block must end at it exactly. Every offset lies inside
+// the ring, so there is no read-back path. A match has no length bound: it is
+// expanded kStep bytes a step. In a step every lane reads its history byte
+// before any lane writes (one LDS read, then one LDS write, of the wave): with
+// off = 65,535 the step's source ring bytes are the ones it writes, shifted by
+// one. The output is periodic in off from o - off on, so lane i of a step at
+// o reads byte o - off + i % off for off < kStep: the bytes just written, a
+// match longer than the ring included (a step k bytes into a match that began
+// at o0 reads o0 - off + (k + i) % off: the phase is folded into o). The flush
+// check runs between steps as between pieces.
+__global__ __launch_bounds__(kLz4Threads) void lz4_inflate_kernel(const uint8_t* __restrict__ src,
+                                                                 const orcg_lz4_chunk* __restrict__ table,
+                                                                 uint8_t* dst, unsigned long long* err) {
+  __shared__ __attribute__((aligned(16))) uint8_t ring[kRing];
+  const int lane = threadIdx.x;
+  const uint32_t ci = blockIdx.x;
+  const orcg_lz4_chunk t = table[ci];
+  const uint32_t n = uni((uint32_t)t.src_bytes);  // the launcher bounds both by 2^31
+  const uint32_t ulen = uni((uint32_t)t.dst_bytes);
+  const uint8_t* csrc = src + uni64(t.src_offset);
+  uint8_t* out = dst + uni64(t.dst_offset);
+  const uint32_t align = uni((uint32_t)(uintptr_t)out & 15u);
+
+  ChunkSrc c;
+  c.adj = uni((uint32_t)(uintptr_t)csrc & 15u);
+  c.rs = __builtin_amdgcn_make_buffer_rsrc((void*)(csrc - c.adj), (short)0, (int)((c.adj + n + 3u) & ~3u), 0x00020000);
+  Slice s;
+  s.valid = false;
+  s.word = 0;
+  s.wbase = 0;
+
+  uint32_t p = 0, o = 0, flushed = 0;  // o <= ulen throughout
+  uint32_t code = kErrNone;
+  const bool stored = uni((uint32_t)t.flags & ORCG_LZ4_STORED) != 0;
+  if (stored && n != ulen) code = kErrLz4;
+  while (code == kErrNone) {
+    // the sequence's literal: a stored chunk is one of the chunk's length
+    uint32_t lit = n, token = 0;
+    if (!stored) {
+      if (p >= n) {
+        code = kErrLz4;
+        break;
+      }
+      token = (uint32_t)peek(c, s, p, lane) & 0xffu;
+      ++p;
+      lit = token >> 4;
+      if (lit == 15 && !lz4_extend(c, s, p, n, lit, min(n - p, ulen - o), lane)) {
+        code = kErrLz4;
+        break;
+      }
+      if (lit > n - p || lit > ulen - o) {
+        code = kErrLz4;
+        break;
+      }
+    }
+    while (lit) {
+      const uint32_t piece = min(lit, kPiece);
+      const uint32_t q = c.adj + p;
+      if (piece <= kStep && s.valid && q >= s.wbase && q + piece <= s.wbase + 256) {
+        // a short literal inside the slice the token came from (the common
+        // sequence): a byte a lane out of the lanes' dwords, no trip to memory.
+        // Every lane takes part in the exchange; lanes past the piece drop theirs.
+        const uint32_t x = q - s.wbase + (uint32_t)lane;
+        const uint32_t w = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(x & ~3u), (int)s.word);
+        if ((uint32_t)lane < piece) ring[(align + o + lane) & kMask] = (uint8_t)(w >> ((x & 3u) * 8));
+        asm volatile("" ::: "memory");
+      } else {
+        lz4_literal_piece(c, ring, align, p, o, piece, lane);
+      }
+      p += piece;
+      o += piece;
+      lit -= piece;
+      if (o - flushed >= kFlush) flushed = flush(ring, out, align, flushed, o, false, lane);
+    }
+    if (p == n) break;  // the block ends with a literal run
+    if (n - p < 2) {
+      code = kErrLz4;
+      break;
+    }
+    const uint32_t off = (uint32_t)peek(c, s, p, lane) & 0xffffu;
+    p += 2;
+    uint32_t len = token & 15u;
+    if (len == 15 && !lz4_extend(c, s, p, n, len, ulen - o, lane)) {
+      code = kErrLz4;
+      break;
+    }
+    len += 4;
+    if (off == 0 || off > o || len > ulen - o) {
+      code = kErrLz4;
+      break;
+    }
+    const uint32_t k = off >= kStep ? (uint32_t)lane : (uint32_t)lane % off;
+    while (len) {
+      const uint32_t step = min(len, kStep);
+      uint32_t b = 0;
+      if ((uint32_t)lane < step) b = ring[(align + o - off + k) & kMask];
+      if ((uint32_t)lane < step) ring[(align + o + lane) & kMask] = (uint8_t)b;
+      asm volatile("" ::: "memory");
+      o += step;
+      len -= step;
+      if (o - flushed >= kFlush) flushed = flush(ring, out, align, flushed, o, false, lane);
+    }
+  }
+  if (code == kErrNone && o != ulen) code = kErrLz4;
+  if (code != kErrNone) {
+    if (lane == 0) report(err, ci, code);
+    return;
+  }
+  flush(ring, out, align, flushed, o, true, lane);
+}
+// (ahead of snappy_inflate_kernel, which stays the unit's last function: its
+// piece of the assembly, the unit's trailer included, is the one of before)
 
 __global__ __launch_bounds__(kSnappyThreads) void snappy_inflate_kernel(const uint8_t* __restrict__ src,
                                                                        const orcg_snappy_chunk* __restrict__ table,
@@ -246,6 +410,15 @@ int launch_snappy_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_snappy_chun
   hipLaunchKernelGGL(snappy_inflate_kernel, dim3((unsigned)nchunks), dim3(kSnappyThreads), 0, ctx->stream, d_src,
                      d_table, d_dst, d_err ? d_err : ctx->d_err);
   return hip_check(ctx, hipGetLastError(), "snappy_inflate_kernel launch");
+}
+
+int launch_lz4_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_lz4_chunk* d_table, uint64_t nchunks, uint8_t* d_dst,
+                       unsigned long long* d_err) {
+  if (nchunks == 0) return ORCG_OK;
+  if (nchunks > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many chunks");
+  hipLaunchKernelGGL(lz4_inflate_kernel, dim3((unsigned)nchunks), dim3(kLz4Threads), 0, ctx->stream, d_src, d_table,
+                     d_dst, d_err ? d_err : ctx->d_err);
+  return hip_check(ctx, hipGetLastError(), "lz4_inflate_kernel launch");
 }
 
 }  // namespace orcg

@@ -1,6 +1,8 @@
-// The host half of the device Snappy path (inflate_kernels.hip): a stream's
-// chunks laid out from their preambles alone. A byte walk over untrusted
-// input; no HIP (tests/cxx/inflate_plan_test.cpp builds it on its own).
+// The host half of the device Snappy and LZ4 paths (inflate_kernels.hip): a
+// stream's chunks laid out without inflating them, Snappy from the preambles,
+// LZ4 from a walk over the sequence tokens. Byte walks over untrusted input;
+// no HIP (tests/cxx/inflate_plan_test.cpp and lz4_plan_test.cpp build it on
+// its own).
 #pragma once
 
 #include <stdint.h>
@@ -39,5 +41,45 @@ bool plan_snappy_chunks(const uint8_t* file, uint64_t file_len, const PlanChunk*
 // orc_file.cpp), then planned as above.
 bool plan_snappy_framed(const uint8_t* bytes, uint64_t len, uint64_t block_size,
                         std::vector<orcg_snappy_chunk>& table, uint64_t* total, const char** err);
+
+// ---- LZ4 (raw blocks) --------------------------------------------------------
+// The same kernel shape (orcg_lz4_device_info). Every LZ4 offset (<= 65,535)
+// lies inside the ring.
+constexpr uint32_t kLz4Ring = kSnappyRing;
+constexpr uint32_t kLz4Threads = kSnappyThreads;
+
+// The decompressed size of one raw LZ4 block in[0, n), at most cap, without
+// copying a byte. These are the decoder's rules in this project (the kernel
+// repeats them), per sequence and in this order:
+//   - no token left (n == 0 included) fails;
+//   - a literal length of 15 is extended by bytes until one is not 255; the
+//     input ending inside the extension fails;
+//   - the literal lies inside the input, and o + literal <= cap;
+//   - the input ending exactly after the literal ends the block, *out_len = o;
+//   - fewer than 2 bytes left for the offset fails;
+//   - a match length of 15 is extended the same way, then 4 is added;
+//   - offset == 0, offset > o and o + match > cap fail;
+//   - a length stops accumulating once it exceeds what can still fit
+//     (min(n - p, cap - o) for a literal, cap - o for a match): no sum wraps
+//     and a lost block's run of 0xFF bytes is not walked to its end.
+// False = the host path's "Corrupt lz4 compressed block" (decompress_chunk).
+//
+// These are the format's safety rules and nothing more. Every block a writer
+// produces is accepted, with liblz4's bytes. On crafted blocks liblz4
+// (LZ4_decompress_safe, which the host path calls) differs in two ways only:
+// 1.9.3 does not check a zero offset (it emits zeros), and it refuses blocks
+// that break its compressor's end-of-block margins (a last literal run shorter
+// than 5 bytes after a match, a match within 12 bytes of the end), which vary
+// by version and with the destination's capacity.
+bool lz4_block_size(const uint8_t* in, uint64_t n, uint64_t cap, uint64_t* out_len);
+
+// As the Snappy pair. A compressed chunk's dst_bytes is its walked size under
+// cap = min(block_size, 2^31 - 1); a block that fails the walk is "Corrupt lz4
+// compressed block".
+bool plan_lz4_chunks(const uint8_t* file, uint64_t file_len, const PlanChunk* chunks, size_t nchunks,
+                     uint64_t block_size, uint64_t dst_base, std::vector<orcg_lz4_chunk>& table, uint64_t* total,
+                     const char** err);
+bool plan_lz4_framed(const uint8_t* bytes, uint64_t len, uint64_t block_size, std::vector<orcg_lz4_chunk>& table,
+                     uint64_t* total, const char** err);
 
 }  // namespace orcg

@@ -25,7 +25,7 @@ constexpr unsigned long long kNoError = ~0ull;
 // (its own tiles; it calls neither launcher above); the Arrow export
 // kScratchNotNull (its entry block), kScratchDense, kScratchColumn; the convert
 // entry points kScratchMisc; the debug hooks kScratchDense, kScratchColumn,
-// kScratchMisc; orcg_snappy_decompress_device kScratchSegments (its chunk table).
+// kScratchMisc; orcg_snappy_decompress_device and orcg_lz4_decompress_device kScratchSegments (the chunk table).
 enum ScratchSlot {
   kScratchStream = 0,       // a host stream's bytes
   kScratchSegments = 1,     // its segment table
@@ -443,6 +443,9 @@ int launch_publish(Ctx* ctx, const PublishArgs& a, uint64_t* d_dst, uint64_t* d_
 // record ((chunk index << 8) | code), null = the context's.
 int launch_snappy_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_snappy_chunk* d_table, uint64_t nchunks,
                           uint8_t* d_dst, unsigned long long* d_err);
+// The same launch for LZ4 chunks (raw blocks; dst_bytes = the host walk's size).
+int launch_lz4_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_lz4_chunk* d_table, uint64_t nchunks,
+                       uint8_t* d_dst, unsigned long long* d_err);
 
 // Dispatch on ctx->rlev2_variant.
 inline int launch_rlev2(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,

@@ -244,7 +244,7 @@ struct ReadOptions {
   // readers share it.
   std::shared_ptr<const ReadPlan> read;
   bool evo_throw = false;
-  // orcg_reader_set_device_decompression: Snappy chunks of raw byte streams
+  // orcg_reader_set_device_decompression: Snappy and LZ4 chunks of raw byte streams
   // ride the upload compressed and inflate on the device
   bool dev_inflate = false;
 };
@@ -285,7 +285,7 @@ struct HostStage {
   // room kept past the prepared bytes for the upload's tail (read-back block
   // and job arena, upload_tail_bytes): upload_and_decode never reallocates
   uint64_t slack = 0;
-  // Snappy streams the device inflates: their chunk table (sources: the
+  // Snappy or LZ4 streams the device inflates: their chunk table (sources: the
   // compressed bytes in staging; destinations in the device-only tail
   // [tail_off, tail_off + tail_bytes) of the stripe's allocation, tail_off >=
   // used + slack), written to staging at inflate_off
@@ -683,7 +683,7 @@ struct orcg_reader {
   // the decodes change: it runs without mu, beside a decode)
   int prepare(uint64_t s, HostStage& hs, const ReadOptions& o) const;
   // whether the stripe's stream (col, slot) is one the host never walks: raw
-  // bytes or varints, which a Snappy file's chunks can inflate on the device
+  // bytes or varints, which a Snappy or LZ4 file's chunks can inflate on the device
   bool host_never_walks(const HostStage& hs, uint32_t col, int slot) const;
   // prepare()'s phases (reader_prepare.cpp). A stream the stripe reads:
   struct Need {

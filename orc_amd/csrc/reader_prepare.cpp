@@ -221,11 +221,13 @@ int orcg_reader::load_streams(HostStage& hs, std::vector<Need>& needs, double* t
     const Need& nd = needs[all[q].first];
     Chunk& ch = needs[all[q].first].chunks[all[q].second];
     if (nd.device) {
-      // the preamble alone: the chunk's length without inflating it
+      // the chunk's length without inflating it: Snappy's preamble alone,
+      // LZ4's size walk (every check of the block runs here)
       const PlanChunk pc{ch.src_off, ch.src_len, ch.original};
       std::vector<orcg_snappy_chunk> one;
       const char* e = "";
-      if (!plan_snappy_chunks(file, file_len, &pc, 1, ps.block_size, 0, one, &ch.dst_len, &e)) {
+      if (!(ps.compression == kLz4 ? plan_lz4_chunks : plan_snappy_chunks)(file, file_len, &pc, 1, ps.block_size, 0,
+                                                                           one, &ch.dst_len, &e)) {
         errs[q] = e;
         bad = true;
       }
@@ -550,9 +552,9 @@ int orcg_reader::prepare(uint64_t s, HostStage& hs, const ReadOptions& o) const 
   std::vector<Need> needs;
   int rc = locate_streams(s, hs, o.selected, o.local_tz, sf, row_index, needs);
   if (rc) return rc;
-  // Snappy chunks of the streams the host never walks inflate on the device
-  // (a block size past the kernel's 32-bit offsets keeps the host path)
-  if (o.dev_inflate && ps.compression == kSnappy && ps.block_size < kSnappyMaxBytes)
+  // Snappy and LZ4 chunks of the streams the host never walks inflate on the
+  // device (a block size past the kernel's 32-bit offsets keeps the host path)
+  if (o.dev_inflate && (ps.compression == kSnappy || ps.compression == kLz4) && ps.block_size < kSnappyMaxBytes)
     for (Need& nd : needs) nd.device = host_never_walks(hs, nd.col, nd.slot);
   double t1 = 0;
   uint64_t w = 0;

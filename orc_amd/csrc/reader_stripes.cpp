@@ -257,12 +257,12 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   if (urc && !rc) rc = fail_ctx(urc);
   if (fl.ev_split && hipEventRecord(fl.ev_up1, act.ctx->stream) != hipSuccess) fl.ev_split = false;
   fl.t1 = now_s();
-  // the stripe's Snappy chunks, ahead of every decode: compressed bytes and
-  // the chunk table rode the upload, the streams land in the tail
+  // the stripe's Snappy or LZ4 chunks, ahead of every decode: compressed bytes
+  // and the chunk table rode the upload, the streams land in the tail
   if (!rc && !hs.inflate.empty()) {
-    if ((rc = launch_snappy_inflate(act.ctx, ds.d_stage, (const orcg_snappy_chunk*)(ds.d_stage + hs.inflate_off),
-                                    hs.inflate.size(), ds.d_stage,
-                                    (unsigned long long*)(ds.d_rb + fl.inflate_word))))
+    const auto launch = ps.compression == file::kLz4 ? launch_lz4_inflate : launch_snappy_inflate;
+    if ((rc = launch(act.ctx, ds.d_stage, (const orcg_snappy_chunk*)(ds.d_stage + hs.inflate_off), hs.inflate.size(),
+                     ds.d_stage, (unsigned long long*)(ds.d_rb + fl.inflate_word))))
       rc = fail_ctx(rc);
     last_dev_inflate[0] += hs.inflate.size();
     for (const orcg_snappy_chunk& k : hs.inflate) last_dev_inflate[1] += k.dst_bytes;

@@ -486,10 +486,11 @@ class Reader:
         check(self._L.orcg_reader_set_lazy_dictionary(self._h, int(bool(on))), self._err)
 
     def set_device_decompression(self, on=True):
-        """Inflate a Snappy file's chunks of raw byte streams (direct string /
-        binary DATA, DICTIONARY_DATA, float / double DATA, varint decimal
-        DATA) on the device instead of the host. Off by default; other codecs
-        ignore it. Row readers created afterwards take it with them."""
+        """Inflate a Snappy or LZ4 file's chunks of raw byte streams (direct
+        string / binary DATA, DICTIONARY_DATA, float / double DATA, varint
+        decimal DATA) on the device instead of the host. Off by default; zlib,
+        zstd and LZO files ignore it. Row readers created afterwards take it
+        with them."""
         check(self._L.orcg_reader_set_device_decompression(self._h, int(bool(on))), self._err)
 
     def last_device_inflate(self):
