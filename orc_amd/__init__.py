@@ -45,5 +45,6 @@ from .lz4 import lz4_decompress_device, lz4_device_info, lz4_plan  # noqa: F401,
 from .timezone import Timezone  # noqa: F401,E402
 
 from .reader import Reader, RowReader, UnionValue, open_reader  # noqa: F401,E402
+from .sarg import SearchArgument, SearchArgumentBuilder  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -245,6 +245,38 @@ SIGNATURES += [
 ]
 
 
+class FilterLiteral(ctypes.Structure):
+    """orcg_literal (include/orcg_filter.h)."""
+
+    _fields_ = [("lo", i64), ("hi", i64), ("d", ctypes.c_double), ("bytes", vp), ("len", u64),
+                ("scale", ctypes.c_int32)]
+
+
+class FilterLeaf(ctypes.Structure):
+    _fields_ = [("op", u32), ("column", u32), ("literal_type", u32), ("nliterals", u32),
+                ("literals", ctypes.POINTER(FilterLiteral))]
+
+
+class FilterOp(ctypes.Structure):
+    _fields_ = [("op", u32), ("arg", u32)]
+
+
+# include/orcg_filter.h
+SIGNATURES += [
+    ("orcg_filter_create", [ctypes.POINTER(FilterLeaf), u32, ctypes.POINTER(FilterOp), u32, ctypes.POINTER(vp)], i32),
+    ("orcg_filter_destroy", [vp], None),
+    ("orcg_filter_last_error", [vp], cp),
+    ("orcg_filter_set_timing", [vp, i32], i32),
+    ("orcg_filter_last_timing", [vp, ctypes.POINTER(ctypes.c_double)], i32),
+    ("orcg_filter_columns_device", [vp, vp, ctypes.POINTER(ColumnView), ctypes.POINTER(TypeInfo), u32, u64,
+                                    ctypes.POINTER(vp), ctypes.POINTER(u64)], i32),
+    ("orcg_filter_gather_device", [vp, vp, u64, u64, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp, vp, vp,
+                                   ctypes.POINTER(u64)], i32),
+    ("orcg_reader_filter_stripe", [vp, u64, vp, ctypes.POINTER(vp), ctypes.POINTER(u64)], i32),
+    ("orcg_reader_filtered_column", [vp, u64, u32, ctypes.POINTER(ColumnView)], i32),
+]
+
+
 class ArrowSchema(ctypes.Structure):
     """struct ArrowSchema (Arrow C Data interface)."""
 

@@ -335,6 +335,11 @@ struct DevSlot {
   unsigned long long* d_errs = nullptr;  // device error record per column (the kernels' atomicMin word)
   uint64_t* d_ones = nullptr;            // per column: non-null rows its PRESENT decode wrote
   std::vector<ColOut> out;
+  // the stripe's last row-level filter run (orcg_reader_filter_stripe): the
+  // selection vector in this slot's arena; dropped with the arena
+  const int64_t* f_selected = nullptr;
+  uint64_t f_count = 0;
+  bool f_valid = false;
 };
 
 // A timed pair of events around a stripe's integer-RLE (kind 0) or byte-RLE

@@ -158,6 +158,7 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   };
   ds.stripe = hs.stripe;
   ds.pool.release_all();
+  ds.f_valid = false;
   // a fresh slot's first chunk: the staging plus ~16 bytes per row and
   // selected column (outputs and scratch); later stripes use what it took
   {

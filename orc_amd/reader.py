@@ -420,9 +420,15 @@ class Reader:
         return ColumnBatch(k, n, nn, data, length, offsets, blob, v.encoding, secondary, tags, index, dict_offsets,
                            scale)
 
-    def read_stripe(self, i):
-        """Decode stripe i on the GPU and copy the selected columns to host."""
+    def read_stripe(self, i, filter=None):
+        """Decode stripe i on the GPU and copy the selected columns to host.
+        filter (a sarg.SearchArgument; Reader.Options.allowSARGToFilter): the
+        rows it selects only, filtered and gathered on the GPU before the copy.
+        Columns that are or lie under a list, map or union are left out of a
+        filtered batch (filter_stripe's row indices still serve them)."""
         self.read_stripe_device(i)
+        if filter is not None:
+            return self._filtered_batch(0, filter)
         cols = {}
         types = self.read_types
         for t in types:
@@ -430,6 +436,61 @@ class Reader:
             if self._L.orcg_reader_column(self._h, t.id, ctypes.byref(v)) != 0 or not v.decoded:
                 continue
             cols[t.id] = self._column(v, t)
+        return Batch(self, cols, types)
+
+    # ---- row-level filter (include/orcg_filter.h, orc_amd/sarg.py)
+
+    def _resolve_column(self, c):
+        if isinstance(c, str):
+            root = self.types[0]
+            if c not in root.field_names:
+                raise _lib.InvalidArgument("no top-level field named %r" % c)
+            return root.subtypes[root.field_names.index(c)]
+        return int(c)
+
+    def filter_stripe_device(self, k, sarg):
+        """Run `sarg` over stripe k of the last read_stripe[s]_device: (device
+        pointer of the ascending int64 row indices, their count). They live in
+        the stripe's device arena until the next read."""
+        h = sarg.handle(self._L, self._resolve_column)
+        p, n = ctypes.c_void_p(), ctypes.c_uint64()
+        check(self._L.orcg_reader_filter_stripe(self._h, k, h, ctypes.byref(p), ctypes.byref(n)), self._err)
+        return p.value, n.value
+
+    def filter_stripe(self, k, sarg):
+        """The rows of stripe k of the last read that `sarg` selects
+        (VectorizedRowBatch.selected), as np.int64."""
+        p, n = self.filter_stripe_device(k, sarg)
+        return self._host(p, 8 * n, np.int64)
+
+    def filtered_column_view(self, k, tid):
+        v = _lib.ColumnView()
+        check(self._L.orcg_reader_filtered_column(self._h, k, tid, ctypes.byref(v)), self._err)
+        return v
+
+    def filtered_column(self, k, tid):
+        """Host copy of column tid of stripe k, the rows its last
+        filter_stripe selected (InvalidArgument "column <id> is not filtered:
+        nested" for a list, map or union column or anything under one)."""
+        return self._column(self.filtered_column_view(k, tid), self.read_types[tid])
+
+    def _filtered_batch(self, k, sarg):
+        self.filter_stripe_device(k, sarg)
+        types = self.read_types
+        nested = set()
+        for t in self.types:
+            if t.kind in (LIST, MAP, UNION) or t.id in nested:
+                nested.add(t.id)
+                nested.update(t.subtypes)
+        cols = {}
+        for t in types:
+            v = _lib.ColumnView()
+            if t.id in nested:
+                continue
+            check(self._L.orcg_reader_stripe_column(self._h, k, t.id, ctypes.byref(v)), self._err)
+            if not v.decoded:  # not selected, or not decodable
+                continue
+            cols[t.id] = self.filtered_column(k, t.id)
         return Batch(self, cols, types)
 
     @property
