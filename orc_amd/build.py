@@ -16,13 +16,13 @@ OUT = os.path.join(HERE, "liborcgpu_prof.so" if PROF else ("liborcgpu_ab.so" if 
 OBJ = os.path.join(HERE, "build_prof" if PROF else ("build_ab" if AB else "build"))
 ARCH = os.environ.get("ORCG_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["rlev2_kernels.hip", "rlev2_tiled.hip", "rlev2_expand.hip", "byterle_kernels.hip", "column_kernels.hip", "rlev1_kernels.hip", "decimal_kernels.hip", "convert_kernels.hip", "arrow_kernels.hip", "inflate_kernels.hip", "filter_kernels.hip", "orcg_ctx.cpp", "pinned.cpp", "host_plan.cpp", "inflate_plan.cpp", "inflate_api.cpp", "filter_plan.cpp", "filter_api.cpp", "host_decode.cpp", "rlev2_api.cpp", "debug_api.cpp",
+SOURCES = ["rlev2_kernels.hip", "rlev2_tiled.hip", "rlev2_expand.hip", "byterle_kernels.hip", "column_kernels.hip", "rlev1_kernels.hip", "decimal_kernels.hip", "convert_kernels.hip", "arrow_kernels.hip", "inflate_kernels.hip", "filter_kernels.hip", "orcg_ctx.cpp", "pinned.cpp", "host_plan.cpp", "rlev2_route.cpp", "inflate_plan.cpp", "inflate_api.cpp", "filter_plan.cpp", "filter_api.cpp", "host_decode.cpp", "rlev2_api.cpp", "debug_api.cpp",
            "multi_launch.cpp", "rlev1_api.cpp", "orc_file.cpp", "reader_api.cpp", "reader_prepare.cpp",
            "reader_collect.cpp", "reader_streams.cpp", "reader_decode.cpp", "reader_fork.cpp", "reader_stripes.cpp",
            "row_reader.cpp", "byterle_api.cpp", "decimal_api.cpp", "convert_api.cpp", "arrow_api.cpp", "arrow_export.cpp", "timezone.cpp", "encoder.cpp", "java_face.cpp"]
 if PROF or AB:
     SOURCES.append("probe_kernels.hip")
-HEADERS = ["orcg_internal.hh", "dev_error.hh", "host_plan.hh", "inflate_plan.hh", "host_decode.hh", "device_util.hh", "rlev2_device.hh", "orc_file.hh", "timezone.hh", "reader_layout.hh", "reader_internal.hh", "read_type.hh", "arrow_internal.hh", "filter_plan.hh", "filter_internal.hh", os.path.join("..", "..", "include", "orcg.h"),
+HEADERS = ["orcg_internal.hh", "dev_error.hh", "host_plan.hh", "rlev2_route.hh", "inflate_plan.hh", "host_decode.hh", "device_util.hh", "rlev2_device.hh", "orc_file.hh", "timezone.hh", "reader_layout.hh", "reader_internal.hh", "read_type.hh", "arrow_internal.hh", "filter_plan.hh", "filter_internal.hh", os.path.join("..", "..", "include", "orcg.h"),
            os.path.join("..", "..", "include", "orcg_reader.h"), os.path.join("..", "..", "include", "orcg_arrow.h"),
            os.path.join("..", "..", "include", "orcg_filter.h")]
 

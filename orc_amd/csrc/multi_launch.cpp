@@ -140,7 +140,16 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
       const RleJob& J = *(const RleJob*)m.d_jobs;
       unsigned long long* const saved = base->d_err;  // the job's own error record
       if (J.err) base->d_err = J.err;
-      rc = launch_rlev2(base, J.src, J.src_len, (int)J.is_signed, J.segtab, J.nsegs, false, 0, 0, J.nvalues, J.dst, 8);
+      Rlev2Args a{};
+      a.src = J.src;
+      a.src_len = J.src_len;
+      a.is_signed = (int)J.is_signed;
+      a.segtab = J.segtab;
+      a.nsegs = J.nsegs;
+      a.nvalues = J.nvalues;
+      a.dst = J.dst;
+      a.dst_bytes = 8;
+      rc = launch_rlev2(base, a);
       base->d_err = saved;
     }
   }

@@ -217,7 +217,7 @@ int orcg_rlev2_variants(int* out, int cap) {
 
 int orcg_ctx_set_rlev2_variant(orcg_ctx* c, int v) {
   // 0 tiled (default), 1 wave-walk; the others pin one tiled instance
-  // (rlev2_tiled.hip launch_rlev2_tiled, rlev2_variant_valid)
+  // (rlev2_route.hh: the ids and rlev2_variant_valid)
   if (!c || !rlev2_variant_valid(v)) return ORCG_INVALID_ARGUMENT;
   c->rlev2_variant = v;
   return ORCG_OK;

@@ -10,6 +10,7 @@
 
 #include "../../include/orcg.h"
 #include "host_plan.hh"
+#include "rlev2_route.hh"
 
 namespace orcg {
 
@@ -99,29 +100,6 @@ void warm_decimal(hipStream_t s);
 // Side streams the file reader may use (ORCG_LANES, default 4; 1 = none).
 unsigned side_lanes();
 
-// One RLEv2 stream of a multi-stream launch: its bytes, segments, output
-// (int64) and value count; seg_base = the launch-wide index of its first
-// segment (set by the launcher). Segments are either a table ({byte offset,
-// value index} per segment) or, for row-index streams of a column without
-// nulls, the row index itself: {byte offset, values to skip, bits} triplets
-// (trip) and the first row of each row group (rows): value index = rows[g] -
-// skip, clamped at 0, as rg_segtab_kernel computes it.
-struct RleJob {
-  const uint8_t* src;
-  uint64_t src_len;
-  const uint64_t* segtab;
-  const int64_t* trip;
-  const int64_t* rows;
-  uint64_t nsegs;
-  void* dst;
-  uint64_t nvalues;
-  uint64_t seg_base;
-  uint32_t is_signed;
-  uint32_t tab_base;  // two-pass launches: the job's first run-table entry (set by the launcher)
-  unsigned long long* err;  // the job's device error record (the reader's per-column word), or null = the launch's
-  const uint64_t* dcount;   // non-null: the value count on the device (nvalues is then the output's capacity)
-};
-
 // One RLEv1 segment of a multi-stream launch, built on the host from the
 // stream's plan or row index: a workgroup reads its whole description in one
 // load (no job search through the table on the device).
@@ -156,16 +134,33 @@ int scratch(Ctx* ctx, ScratchSlot slot, size_t bytes, void** out);
 // Wait for the context stream and fold the device error record into a status.
 int sync_ctx(Ctx* ctx);
 
-// Kernel launchers (rlev2_kernels.hip). segtab is either orcg_segment[] or the
-// row-index positions array (positions_mode, with rows_per_group).
+// One RLEv2 stream's launch: values [value_begin, value_begin + nvalues) of
+// the stream at `src` (device) into dst, as integers of dst_bytes (8, 4 or 2).
+// segtab is either orcg_segment[] or the row-index positions array
+// (`positions`, with rows_per_group). dcount (may be null; the tiled
+// instances only): the value count on the device, nvalues then bounds the
+// output only.
+struct Rlev2Args {
+  const uint8_t* src;
+  uint64_t src_len;
+  int is_signed;
+  const uint64_t* segtab;
+  uint64_t nsegs;
+  bool positions;
+  uint64_t rows_per_group;
+  uint64_t value_begin;
+  uint64_t nvalues;
+  void* dst;
+  int dst_bytes;
+  const uint64_t* dcount;
+};
+
+// The wave-walk kernel (rlev2_kernels.hip).
 // java: 0 = the C++ reader's rules; 1 = Java's RunLengthIntegerReaderV2
 // (DELTA runs of one value with a bit width decode two values, PATCHED_BASE
 // with pl == 0 fails as Java's array index, pw + pgw > 64 fails with Java's
 // IOException); 2 = Java with skipCorrupt (pw + pgw > 64 decodes, :196-202).
-int launch_rlev2_decode(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                        const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode,
-                        uint64_t rows_per_group, uint64_t value_begin, uint64_t nvalues,
-                        void* d_dst, int dst_bytes, int java = 0);
+int launch_rlev2_decode(Ctx* ctx, const Rlev2Args& a, int java = 0);
 
 
 // Two-pass short-run RLEv2 decode (DESIGN.md §3.1 "Two passes"): the union
@@ -180,40 +175,25 @@ int launch_rlev2_decode(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is
 // offset | its first value (segment-relative) << 32. Runs of passes the first
 // kernel expands itself (long runs, values past spg * slice) are not tabled.
 constexpr uint32_t kRtHdr = 6;
-constexpr uint32_t kSliceMax = 1024;
 struct RunTab {
   uint64_t* tab;
   uint32_t* hdr;
   uint32_t spg;
   uint32_t slice;
 };
-// The second pass over `nsegs` launch-wide segments (single stream: d_src ..
-// d_count as launch_rlev2_tiled; multi-stream: jobs_d, int64 output).
-int launch_rlev2_expand(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed, uint64_t value_begin,
-                        uint64_t nvalues, void* d_dst, int dst_bytes, const uint64_t* d_count, const RleJob* jobs_d,
-                        uint32_t njobs, uint64_t nsegs, const RunTab& rt);
+// The second pass over a.nsegs launch-wide segments (single stream: `a` as
+// launch_rlev2_tiled took it; multi-stream: jobs_d, int64 output).
+int launch_rlev2_expand(Ctx* ctx, const Rlev2Args& a, const RleJob* jobs_d, uint32_t njobs, const RunTab& rt);
 void warm_rlev2_expand(hipStream_t s);
 
-// RLEv2 kernel variants a context accepts (orcg_rlev2_variants): 0 default,
-// 1 wave-walk, and pins of single tiled instances (launch_rlev2_tiled): 2-8
-// the default's instances and their one-pass / drain forms, 9 = 2 without the
-// flat DIRECT prologue, 10 = 2 with the prologue's 8-byte form at every width
-// (no 16-byte chunks for W=64).
-constexpr int kMaxRlev2Variant = 10;
-bool rlev2_variant_valid(int v);
-// d_count (may be null): the value count on the device, nvalues then
-// bounds the output only.
-int launch_rlev2_tiled(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                       const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode,
-                       uint64_t rows_per_group, uint64_t value_begin, uint64_t nvalues,
-                       void* d_dst, int dst_bytes, const uint64_t* d_count = nullptr);
+// A tiled instance (rlev2_tiled.hip): the pinned one, or the one the default
+// routes the stream to (rlev2_route.hh, which also lists the variants).
+int launch_rlev2_tiled(Ctx* ctx, const Rlev2Args& a);
 
 // Every stream of `jobs` (segment-table mode, int64 output) in one launch per
 // instance the default's density rule picks (or the pinned variant);
 // variant 1 falls back to one launch per stream.
 int launch_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs);
-// Variants whose instances take job tables with row-index segments (RleJob::trip).
-bool rlev2_multi_capable(int variant);
 // Copies a job table into the context's arena (no copy enqueued) or its
 // pinned ring and device mirror (an H2D ordered on ctx->stream); *out = the
 // device copy.
@@ -448,15 +428,9 @@ int launch_lz4_inflate(Ctx* ctx, const uint8_t* d_src, const orcg_lz4_chunk* d_t
                        uint8_t* d_dst, unsigned long long* d_err);
 
 // Dispatch on ctx->rlev2_variant.
-inline int launch_rlev2(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                        const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode,
-                        uint64_t rows_per_group, uint64_t value_begin, uint64_t nvalues,
-                        void* d_dst, int dst_bytes) {
-  if (ctx->rlev2_variant == ORCG_RLEV2_WAVE_WALK)
-    return launch_rlev2_decode(ctx, d_src, src_len, is_signed, d_segtab, nsegs, positions_mode,
-                               rows_per_group, value_begin, nvalues, d_dst, dst_bytes);
-  return launch_rlev2_tiled(ctx, d_src, src_len, is_signed, d_segtab, nsegs, positions_mode,
-                            rows_per_group, value_begin, nvalues, d_dst, dst_bytes);
+static_assert(kRlev2Default == ORCG_RLEV2_TILED && kRlev2WaveWalk == ORCG_RLEV2_WAVE_WALK, "the public numbers");
+inline int launch_rlev2(Ctx* ctx, const Rlev2Args& a) {
+  return ctx->rlev2_variant == kRlev2WaveWalk ? launch_rlev2_decode(ctx, a) : launch_rlev2_tiled(ctx, a);
 }
 
 }  // namespace orcg

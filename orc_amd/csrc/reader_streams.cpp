@@ -104,8 +104,17 @@ int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t
   madd(kMDecodeCall, 1);
   rc = timed(0, [&]() -> int {
     if (v1) return launch_rlev1(act.ctx, d_src, sb.len, sg, d_seg, nseg, 0, count, out, 8);
-    return dcount ? launch_rlev2_tiled(act.ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8, dcount)
-                  : launch_rlev2(act.ctx, d_src, sb.len, sg, d_seg, nseg, false, 0, 0, count, out, 8);
+    Rlev2Args a{};
+    a.src = d_src;
+    a.src_len = sb.len;
+    a.is_signed = sg;
+    a.segtab = d_seg;
+    a.nsegs = nseg;
+    a.nvalues = count;
+    a.dst = out;
+    a.dst_bytes = 8;
+    a.dcount = dcount;
+    return dcount ? launch_rlev2_tiled(act.ctx, a) : launch_rlev2(act.ctx, a);
   });
   return rc ? fail_ctx(rc) : ORCG_OK;
 }

@@ -14,8 +14,16 @@ namespace {
 // over a staged host stream.
 HostLaunch rlev2_launch(Ctx* c, int is_signed, int width, int java = 0) {
   return [=](const uint8_t* d_src, uint64_t len, const uint64_t* d_seg, uint64_t nsegs, uint64_t count, void* d_out) {
-    return java ? launch_rlev2_decode(c, d_src, len, is_signed, d_seg, nsegs, false, 0, 0, count, d_out, width, java)
-                : launch_rlev2(c, d_src, len, is_signed, d_seg, nsegs, false, 0, 0, count, d_out, width);
+    Rlev2Args a{};
+    a.src = d_src;
+    a.src_len = len;
+    a.is_signed = is_signed;
+    a.segtab = d_seg;
+    a.nsegs = nsegs;
+    a.nvalues = count;
+    a.dst = d_out;
+    a.dst_bytes = width;
+    return java ? launch_rlev2_decode(c, a, java) : launch_rlev2(c, a);
   };
 }
 
@@ -58,8 +66,17 @@ int orcg_rlev2_decode_device(orcg_ctx* c, const uint8_t* d_src, uint64_t src_len
                              uint64_t nvalues, void* d_dst, int dst_bytes) {
   if (!c || (nsegs && (!d_src || !d_segs)) || (nvalues && !d_dst)) return ORCG_INVALID_ARGUMENT;
   hipSetDevice(c->device);
-  return launch_rlev2(c, d_src, src_len, is_signed, (const uint64_t*)d_segs, nsegs, false, 0,
-                             value_begin, nvalues, d_dst, dst_bytes);
+  Rlev2Args a{};
+  a.src = d_src;
+  a.src_len = src_len;
+  a.is_signed = is_signed;
+  a.segtab = (const uint64_t*)d_segs;
+  a.nsegs = nsegs;
+  a.value_begin = value_begin;
+  a.nvalues = nvalues;
+  a.dst = d_dst;
+  a.dst_bytes = dst_bytes;
+  return launch_rlev2(c, a);
 }
 
 int orcg_rlev2_decode_positions_device(orcg_ctx* c, const uint8_t* d_src, uint64_t src_len,
@@ -69,8 +86,19 @@ int orcg_rlev2_decode_positions_device(orcg_ctx* c, const uint8_t* d_src, uint64
   if (!c || (ngroups && (!d_src || !d_positions)) || (nvalues && !d_dst) || rows_per_group == 0)
     return ORCG_INVALID_ARGUMENT;
   hipSetDevice(c->device);
-  return launch_rlev2(c, d_src, src_len, is_signed, d_positions, ngroups, true,
-                             rows_per_group, value_begin, nvalues, d_dst, dst_bytes);
+  Rlev2Args a{};
+  a.src = d_src;
+  a.src_len = src_len;
+  a.is_signed = is_signed;
+  a.segtab = d_positions;
+  a.nsegs = ngroups;
+  a.positions = true;
+  a.rows_per_group = rows_per_group;
+  a.value_begin = value_begin;
+  a.nvalues = nvalues;
+  a.dst = d_dst;
+  a.dst_bytes = dst_bytes;
+  return launch_rlev2(c, a);
 }
 
 // ---- host-buffer decode ----------------------------------------------------

@@ -456,27 +456,26 @@ __global__ void warm_rlev2_expand_kernel() {}
 
 }  // namespace
 
-int launch_rlev2_expand(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed, uint64_t value_begin,
-                        uint64_t nvalues, void* d_dst, int dst_bytes, const uint64_t* d_count, const RleJob* jobs_d,
-                        uint32_t njobs, uint64_t nsegs, const RunTab& rt) {
+int launch_rlev2_expand(Ctx* ctx, const Rlev2Args& a, const RleJob* jobs_d, uint32_t njobs, const RunTab& rt) {
   if (!rt.tab || !rt.hdr || rt.spg == 0 || rt.slice == 0 || rt.slice > kSliceMax || rt.slice % kThreads)
     return set_error(ctx, ORCG_INVALID_ARGUMENT, "bad run table");
-  const uint64_t grid = nsegs * rt.spg;
+  const uint64_t grid = a.nsegs * rt.spg;
   if (grid == 0) return ORCG_OK;
   if (grid > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many slices");
   const dim3 g((unsigned)grid), b(kThreads);
-if (jobs_d) {
+  const int sg = a.is_signed ? 1 : 0;
+  if (jobs_d) {
     hipLaunchKernelGGL((rlev2_expand_kernel<int64_t, true>), g, b, 0, ctx->stream, nullptr, 0, 0, 0, 0, nullptr,
                        nullptr, jobs_d, njobs, rt);
-  } else if (dst_bytes == 8) {
-    hipLaunchKernelGGL((rlev2_expand_kernel<int64_t, false>), g, b, 0, ctx->stream, d_src, src_len, is_signed,
-                       value_begin, nvalues, (int64_t*)d_dst, d_count, nullptr, 0, rt);
-  } else if (dst_bytes == 4) {
-    hipLaunchKernelGGL((rlev2_expand_kernel<int32_t, false>), g, b, 0, ctx->stream, d_src, src_len, is_signed,
-                       value_begin, nvalues, (int32_t*)d_dst, d_count, nullptr, 0, rt);
+  } else if (a.dst_bytes == 8) {
+    hipLaunchKernelGGL((rlev2_expand_kernel<int64_t, false>), g, b, 0, ctx->stream, a.src, a.src_len, sg,
+                       a.value_begin, a.nvalues, (int64_t*)a.dst, a.dcount, nullptr, 0, rt);
+  } else if (a.dst_bytes == 4) {
+    hipLaunchKernelGGL((rlev2_expand_kernel<int32_t, false>), g, b, 0, ctx->stream, a.src, a.src_len, sg,
+                       a.value_begin, a.nvalues, (int32_t*)a.dst, a.dcount, nullptr, 0, rt);
   } else {
-    hipLaunchKernelGGL((rlev2_expand_kernel<int16_t, false>), g, b, 0, ctx->stream, d_src, src_len, is_signed,
-                       value_begin, nvalues, (int16_t*)d_dst, d_count, nullptr, 0, rt);
+    hipLaunchKernelGGL((rlev2_expand_kernel<int16_t, false>), g, b, 0, ctx->stream, a.src, a.src_len, sg,
+                       a.value_begin, a.nvalues, (int16_t*)a.dst, a.dcount, nullptr, 0, rt);
   }
   return hip_check(ctx, hipGetLastError(), "rlev2_expand_kernel launch");
 }

@@ -389,19 +389,16 @@ __global__ __launch_bounds__(kWave) void rlev2_decode_kernel(
 
 }  // namespace
 
-int launch_rlev2_decode(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                        const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode,
-                        uint64_t rows_per_group, uint64_t value_begin, uint64_t nvalues,
-                        void* d_dst, int dst_bytes, int java) {
-  if (nsegs == 0 || nvalues == 0) return ORCG_OK;
-  if (nsegs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
-  if (src_len >= (1ull << 56)) return set_error(ctx, ORCG_INVALID_ARGUMENT, "stream too long");
-  if (java && positions_mode) return set_error(ctx, ORCG_INVALID_ARGUMENT, "Java rules take segment tables");
-  const dim3 grid((unsigned)nsegs), block(kWave);
-  const int sg = is_signed ? 1 : 0;
-#define ORCG_LAUNCH1(T, P, J)                                                                     \
-  hipLaunchKernelGGL((rlev2_decode_kernel<T, P, J>), grid, block, 0, ctx->stream, d_src, src_len, \
-                     sg, d_segtab, nsegs, rows_per_group, value_begin, nvalues, (T*)d_dst,        \
+int launch_rlev2_decode(Ctx* ctx, const Rlev2Args& a, int java) {
+  if (a.nsegs == 0 || a.nvalues == 0) return ORCG_OK;
+  if (a.nsegs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
+  if (a.src_len >= (1ull << 56)) return set_error(ctx, ORCG_INVALID_ARGUMENT, "stream too long");
+  if (java && a.positions) return set_error(ctx, ORCG_INVALID_ARGUMENT, "Java rules take segment tables");
+  const dim3 grid((unsigned)a.nsegs), block(kWave);
+  const int sg = a.is_signed ? 1 : 0;
+#define ORCG_LAUNCH1(T, P, J)                                                                         \
+  hipLaunchKernelGGL((rlev2_decode_kernel<T, P, J>), grid, block, 0, ctx->stream, a.src, a.src_len,   \
+                     sg, a.segtab, a.nsegs, a.rows_per_group, a.value_begin, a.nvalues, (T*)a.dst,    \
                      ctx->d_err)
 #define ORCG_LAUNCH(T, P)                                  \
   do {                                                     \
@@ -409,15 +406,15 @@ int launch_rlev2_decode(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is
     else if (java == 1) ORCG_LAUNCH1(T, false, 1);         \
     else ORCG_LAUNCH1(T, P, 0);                            \
   } while (0)
-  switch (dst_bytes) {
+  switch (a.dst_bytes) {
     case 8:
-      if (positions_mode) ORCG_LAUNCH(int64_t, true); else ORCG_LAUNCH(int64_t, false);
+      if (a.positions) ORCG_LAUNCH(int64_t, true); else ORCG_LAUNCH(int64_t, false);
       break;
     case 4:
-      if (positions_mode) ORCG_LAUNCH(int32_t, true); else ORCG_LAUNCH(int32_t, false);
+      if (a.positions) ORCG_LAUNCH(int32_t, true); else ORCG_LAUNCH(int32_t, false);
       break;
     case 2:
-      if (positions_mode) ORCG_LAUNCH(int16_t, true); else ORCG_LAUNCH(int16_t, false);
+      if (a.positions) ORCG_LAUNCH(int16_t, true); else ORCG_LAUNCH(int16_t, false);
       break;
     default:
       return set_error(ctx, ORCG_INVALID_ARGUMENT, "dst_bytes must be 8, 4 or 2");

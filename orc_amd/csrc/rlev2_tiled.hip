@@ -1947,14 +1947,12 @@ __global__ __launch_bounds__(kThreads, kMinWaves) void rlev2_tiled_kernel(
 
 }  // namespace
 
-// Variants (ctx->rlev2_variant, include/orcg.h): 0 = the density-adaptive
-// default; 2-10 pin one instance (the parity tests run each: 6 = the union
-// instance in two passes, the default's below 1.25 B/value; 8 = the same in
-// one pass; 9 = instance 2 without the flat DIRECT path, its in-binary A/B
-// control; 10 = instance 2 with the flat path's 8-byte form for every width,
-// the A/B control and parity cover of flat_expand at W=64); 1 = the
-// wave-walk kernel (rlev2_kernels.hip).
-bool rlev2_variant_valid(int v) { return v >= 0 && v <= kMaxRlev2Variant; }
+// The host half: the instance table and the launchers. Which instance a
+// stream gets (ctx->rlev2_variant, include/orcg.h: 0 = the density-adaptive
+// default, kRlev2FirstTiled .. kMaxRlev2Variant pin one instance, 1 = the
+// wave-walk kernel of rlev2_kernels.hip), one pass or two, and the grouping
+// of multi-stream launches are rlev2_route.hh's; what needs the device (the
+// CU count, the queue, the run table, the launches) is here.
 
 static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
   // {stamp, byte offset, value index} per launch-wide segment, stamps zeroed
@@ -1977,28 +1975,6 @@ static int defer_queue(Ctx* ctx, uint64_t nsegs, unsigned long long** out) {
   return ORCG_OK;
 }
 
-// The default's instance for a stream, by its stream bytes per value
-// (profiles/r03/sweep.md):
-//  * >= 5 B/value (wide values, W >= 40): 33 KB windows (4 WG/CU) filled
-//    through registers, one walking wave, no queue (writers emit wide random
-//    values in long DIRECT runs; the empty queue drain cost 4 us of C2's 290);
-//    a segment's leading chain of equal full DIRECT runs skips the windows
-//    altogether (kOptFlat);
-//  * 1.25 - 5 B/value: 21 KB serial windows (6 WG/CU), queueing segments whose
-//    first runs are short by values for the dense drain (long DIRECT / DELTA /
-//    PATCHED_BASE runs of 10-40-bit values: 5.3-6.1 TB/s; short runs of wide
-//    values 20 % slower than the union instance, the price of the rule);
-//  * < 1.25 B/value (low-cardinality columns, SHORT_REPEAT 0.2-1 B/value): the
-//    union instance, which routes each window by its own runs (8.5 KB dense
-//    windows with parallel run discovery, 16.75 KB serial windows once a
-//    segment's runs are long).
-// The dense-capable instances walk long runs 15-20 % slower than the serial
-// ones (at 6 WG/CU they carry 56 B/lane of scratch, the serial ones none), so long-run
-// streams above 1.25 B/value stay on the serial instance.
-static int default_variant(uint64_t src_len, uint64_t est_values) {
-  return src_len >= 5 * est_values ? 2 : (4 * src_len >= 5 * est_values ? 3 : 6);
-}
-
 static int cu_count(Ctx* ctx) {
   if (ctx->num_cus == 0) {
     int cus = 0;
@@ -2009,25 +1985,6 @@ static int cu_count(Ctx* ctx) {
   return ctx->num_cus;
 }
 
-// The union instance runs in two passes (kOptTable + rlev2_expand_kernel)
-// when its launch has at most this many segments per CU: a launch of a few
-// segments per CU lasts as long as its slowest segments' discovery +
-// expansion, and balancing the expansion by values pays (configs[3]'s
-// multi-stream launch, 1,336 segments: 297 -> 150 + 86 us; configs[4]'s
-// child streams, 264: 93 -> 57 + 20 us); with many more segments than the
-// chip holds at once, the one-pass instance's expansion already overlaps
-// other workgroups' discovery and the second pass only adds its own latency
-// and the run table's traffic (the stream sweep's 10,000-segment launches:
-// SHORT_REPEAT 12-bit 2,016 GB/s in one pass, 1,267 in two; profiles/r06/
-// sweep_*).
-constexpr uint64_t kTwoPassSegsPerCu = 12;
-static int union_variant(Ctx* ctx, uint64_t nsegs) {
-  return nsegs <= kTwoPassSegsPerCu * (uint64_t)cu_count(ctx) ? 6 : 8;
-}
-
-// One launch (or serial + drain pair) of instance `variant` over nsegs
-// segments of one stream, or (jobs_d) over the launch-wide segments of a
-// device job table.
 // ORCG_DEBUG_DEFER: after a serial launch, how many of its segments it
 // queued for the dense drain (stderr; synchronises the stream)
 static void debug_defer(Ctx* ctx, const unsigned long long* dq, uint64_t nsegs, uint32_t dpar) {
@@ -2040,26 +1997,6 @@ static void debug_defer(Ctx* ctx, const unsigned long long* dq, uint64_t nsegs, 
   for (uint64_t g = 0; g < nsegs; ++g) q += h[3 * g] == dpar ? 1 : 0;
   fprintf(stderr, "defer: %llu of %llu segments queued (any %d)\n", (unsigned long long)q,
           (unsigned long long)nsegs, h[3 * nsegs] == dpar ? 1 : 0);
-}
-
-// Two-pass shape for segments of at most `seg_values` values (a bound: a
-// segment that turns out longer has its later passes expanded by the first
-// kernel): slices of <= kSliceMax values, a multiple of 256, spg per segment.
-static void two_pass_shape(uint64_t seg_values, uint32_t* spg, uint32_t* slice) {
-  const uint64_t n = std::max<uint64_t>(seg_values, 1);
-  const uint64_t smax = kSliceMax;
-  const uint64_t k = std::min<uint64_t>((n + smax - 1) / smax, 256);
-  uint64_t s = (n + k - 1) / k;
-  s = std::min<uint64_t>((s + 255) & ~255ull, smax);
-  *spg = (uint32_t)k;
-  *slice = (uint32_t)s;
-}
-
-// A segment's value bound for the two-pass shape: its share of the values,
-// + 1/8 and one run (row-index segments start up to 511 values early).
-static uint64_t seg_value_bound(uint64_t values, uint64_t nsegs) {
-  const uint64_t avg = (values + nsegs - 1) / std::max<uint64_t>(nsegs, 1);
-  return avg + avg / 8 + 512;
 }
 
 // The context's run table (entries) and segment headers (nsegs x (kRtHdr +
@@ -2092,142 +2029,134 @@ static int runtab_buffers(Ctx* ctx, uint64_t entries, uint64_t nsegs, uint32_t s
   return ORCG_OK;
 }
 
-static int launch_tiled(Ctx* ctx, int variant, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                        const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode, uint64_t rows_per_group,
-                        uint64_t value_begin, uint64_t nvalues, void* d_dst, int dst_bytes, const RleJob* jobs_d,
-                        uint32_t njobs_d, const uint64_t* dcount = nullptr, const MultiLaunch* ml = nullptr) {
-  if (nsegs == 0 || nvalues == 0) return ORCG_OK;
-  RunTab rtab{nullptr, nullptr, 0, 0};
-  if (variant == 6) {
-    // the union instance in two passes, when the run table can address the
-    // stream (u32 entries and offsets)
-    uint64_t entries = 0, bound = 0;
-    uint32_t spg = 0, slice = 0;
-    if (jobs_d) {
-      if (ml && ml->spg) {
-        entries = ml->tab_entries;
-        spg = ml->spg;
-        slice = ml->slice;
-      }
-    } else if (src_len < 0xffff0000ull && nsegs < 0x7fff0000ull) {
-      entries = src_len / 2 + nsegs + 1;
-      bound = positions_mode ? rows_per_group + 512 : seg_value_bound(nvalues, nsegs);
-      two_pass_shape(bound, &spg, &slice);
-    }
-    if (spg && entries < 0xffff0000ull && nsegs * spg < 0x7fffffffull) {
-      const int rc = runtab_buffers(ctx, entries, nsegs, spg, slice, &rtab);
-      if (rc) return rc;
-    } else {
-      variant = 8;  // one pass
-    }
+// One launch of an instance: a stream's arguments, or (jobs) the launch-wide
+// segments a.nsegs and values a.nvalues of a device job table; the queue of a
+// serial + drain pair and the run table of a two-pass launch.
+struct TiledLaunch {
+  Rlev2Args a;
+  const RleJob* jobs;
+  uint32_t njobs;
+  unsigned long long* dq;
+  uint32_t dpar;
+  RunTab rtab;
+};
+using Enqueue = void (*)(Ctx*, const TiledLaunch&);
+
+template <typename T, typename Kernel>
+static void enqueue_kernel(Ctx* ctx, const TiledLaunch& l, Kernel kernel) {
+  const Rlev2Args& a = l.a;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)a.nsegs), dim3(kThreads), 0, ctx->stream, a.src, a.src_len,
+                     a.is_signed ? 1 : 0, a.segtab, a.nsegs, a.rows_per_group, a.value_begin, a.nvalues, (T*)a.dst,
+                     ctx->d_err, l.dq, l.dpar, l.jobs, l.njobs, a.dcount, l.rtab);
+}
+// An instance, K = (options, window KB, min waves, kDense, kDefer): its
+// multi-stream kernel and its single-stream ones. (All seven are named in
+// this one body, so the code object holds the kernels instance by instance in
+// kInstances' order: scripts/isa_diff.py compares its metadata as one piece.)
+template <int... K>
+static void enqueue(Ctx* ctx, const TiledLaunch& l) {
+  const bool pos = l.a.positions;
+  if (l.jobs) {
+    enqueue_kernel<int64_t>(ctx, l, rlev2_tiled_kernel<int64_t, false, K..., true>);
+  } else if (l.a.dst_bytes == 8) {
+    if (pos) enqueue_kernel<int64_t>(ctx, l, rlev2_tiled_kernel<int64_t, true, K..., false>);
+    else enqueue_kernel<int64_t>(ctx, l, rlev2_tiled_kernel<int64_t, false, K..., false>);
+  } else if (l.a.dst_bytes == 4) {
+    if (pos) enqueue_kernel<int32_t>(ctx, l, rlev2_tiled_kernel<int32_t, true, K..., false>);
+    else enqueue_kernel<int32_t>(ctx, l, rlev2_tiled_kernel<int32_t, false, K..., false>);
+  } else {
+    if (pos) enqueue_kernel<int16_t>(ctx, l, rlev2_tiled_kernel<int16_t, true, K..., false>);
+    else enqueue_kernel<int16_t>(ctx, l, rlev2_tiled_kernel<int16_t, false, K..., false>);
   }
-  if (nsegs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
-  if (dst_bytes != 8 && dst_bytes != 4 && dst_bytes != 2)
-    return set_error(ctx, ORCG_INVALID_ARGUMENT, "dst_bytes must be 8, 4 or 2");
-  const dim3 block(kThreads);
-  const int sg = is_signed ? 1 : 0;
-  unsigned long long* dq = nullptr;
-  uint32_t dpar = 0;
-  (void)cu_count(ctx);
-
-#define ORCG_K(T, P, O, WKB, ML)                                                                          \
-  hipLaunchKernelGGL((rlev2_tiled_kernel<T, P, O, WKB, MW, DN, DF, ML>), grid, block, 0, ctx->stream,     \
-                     d_src, src_len, sg, d_segtab, nsegs, rows_per_group, value_begin, nvalues, (T*)d_dst, \
-                     ctx->d_err, dq, dpar, jobs_d, njobs_d, dcount, rtab)
-// an instance (options, window KB, min waves, kDense, kDefer): its
-// single-stream kernels and its multi-stream one
-#define ORCG_KX(O, WKB, MWV, DNV, DFV, GRIDV)                 \
-  do {                                                        \
-    constexpr int MW = MWV;                                   \
-    constexpr int DN = (int)(DNV);                            \
-    constexpr int DF = DFV;                                   \
-    const dim3 grid(GRIDV);                                   \
-    if (jobs_d) {                                             \
-      ORCG_K(int64_t, false, O, WKB, true);                   \
-    } else if (dst_bytes == 8) {                              \
-      if (positions_mode) ORCG_K(int64_t, true, O, WKB, false); \
-      else ORCG_K(int64_t, false, O, WKB, false);             \
-    } else if (dst_bytes == 4) {                              \
-      if (positions_mode) ORCG_K(int32_t, true, O, WKB, false); \
-      else ORCG_K(int32_t, false, O, WKB, false);             \
-    } else {                                                  \
-      if (positions_mode) ORCG_K(int16_t, true, O, WKB, false); \
-      else ORCG_K(int16_t, false, O, WKB, false);             \
-    }                                                         \
-  } while (0)
-
-  // the default's instances
-  constexpr int kSer = 0;             // LDS-DMA windows
-  constexpr int kWide = kOptRegFill;  // register-filled windows
-  // a serial instance that queues short-run segments, then the dense
-  // instance that drains the queue
-#define ORCG_DEFERRING(O, WKB, MWV, DO)                                     \
-  do {                                                                      \
-    int rc_ = defer_queue(ctx, nsegs, &dq);                                 \
-    if (rc_) return rc_;                                                    \
-    dpar = (uint32_t)(ctx->defer_seq++ % 0xffffffffull) + 1u; /* never 0 */ \
-    ORCG_KX(O, WKB, MWV, 0, 1, (unsigned)nsegs);                            \
-    debug_defer(ctx, dq, nsegs, dpar);                                      \
-    ORCG_KX(DO, 8, 6, 2, 2, (unsigned)nsegs);                               \
-  } while (0)
-
-  const unsigned grid_s = (unsigned)nsegs;
-  switch (variant) {
-    case 2:  // 33 KB register-filled serial, no queue, flat DIRECT prologue (W=64 runs in 16-byte chunks)
-      ORCG_KX(kWide | kOptFlat | kOptFlat16, 33, 1, 0, 0, grid_s);
-      break;
-    case 3: ORCG_DEFERRING(kSer, 21, 6, kSer); break;  // 21 KB serial + dense drain
-    case 4: ORCG_KX(kSer, 8, 6, 2, 0, grid_s); break;   // dense-capable, 8.5 KB
-    case 5: ORCG_KX(kSer, 12, 5, 2, 0, grid_s); break;  // dense-capable, 12.5 KB
-    case 6: {
-      // union, two passes: dense passes table their runs, rlev2_expand_kernel
-      // expands them in value slices
-      ORCG_KX(kSer | kOptUnion | kOptTable, 8, 6, 2, 0, grid_s);
-      const int rc = hip_check(ctx, hipGetLastError(), "rlev2_tiled_kernel launch");
-      if (rc) return rc;
-      return launch_rlev2_expand(ctx, d_src, src_len, sg, value_begin, nvalues, d_dst, dst_bytes, dcount, jobs_d,
-                                 njobs_d, nsegs, rtab);
-    }
-    case 7: ORCG_DEFERRING(kWide, 33, 1, kSer); break;  // 33 KB serial + dense drain (round-3 default, A/B)
-    case 8: ORCG_KX(kSer | kOptUnion, 8, 6, 2, 0, grid_s); break;  // union in one pass (round-5 default)
-    case 9: ORCG_KX(kWide, 33, 1, 0, 0, grid_s); break;  // 2 without the flat prologue (A/B control)
-    case 10: ORCG_KX(kWide | kOptFlat, 33, 1, 0, 0, grid_s); break;  // 2 without kOptFlat16 (A/B control)
-    default: return set_error(ctx, ORCG_INVALID_ARGUMENT, "unknown RLEv2 kernel variant");
-  }
-#undef ORCG_DEFERRING
-#undef ORCG_KX
-#undef ORCG_K
-  return hip_check(ctx, hipGetLastError(), "rlev2_tiled_kernel launch");
 }
 
-int launch_rlev2_tiled(Ctx* ctx, const uint8_t* d_src, uint64_t src_len, int is_signed,
-                       const uint64_t* d_segtab, uint64_t nsegs, bool positions_mode,
-                       uint64_t rows_per_group, uint64_t value_begin, uint64_t nvalues, void* d_dst,
-                       int dst_bytes, const uint64_t* d_count) {
-  int variant = ctx->rlev2_variant;
-  if (variant == 0) {
-    const uint64_t est = positions_mode ? nsegs * rows_per_group : nvalues;
-    variant = default_variant(src_len, est);
-    if (variant == 6) variant = union_variant(ctx, nsegs);
-    // more than 8.1 stream bytes a value is more than any 64-bit payload:
-    // the excess is run headers, i.e. runs of ~20 values or fewer of wide
-    // values (short DIRECT / PATCHED_BASE), whose expansion the two-pass
-    // union balances by values at any segment count (sweep short DIRECT
-    // 64-bit, 10,000 segments: 217 GB/s in the serial walk, 270 in one union
-    // pass, 379 in two; profiles/r06/sweep_shortdirect_64_548c478.jsonl).
-    // 512-value W=64 runs (configs[1]) are 8.004 B/value: the serial walk.
-    else if (variant == 2 && 10 * src_len > 81 * est) variant = 6;
+constexpr int kSer = 0;             // LDS-DMA windows
+constexpr int kWide = kOptRegFill;  // register-filled windows
+// The instances: enqueue<options, window KB, min waves, kDense, kDefer>, and
+// for a serial instance that queues short-run segments (kDefer 1) the dense
+// instance that drains the queue (kDefer 2).
+struct Instance {
+  int id;
+  Enqueue launch, drain;
+};
+constexpr Instance kInstances[] = {
+    // 33 KB register-filled serial, no queue, flat DIRECT prologue (W=64 runs in 16-byte chunks)
+    {kRlev2Wide, enqueue<kWide | kOptFlat | kOptFlat16, 33, 1, 0, 0>, nullptr},
+    // 21 KB serial + dense drain
+    {kRlev2SerialDrain, enqueue<kSer, 21, 6, 0, 1>, enqueue<kSer, 8, 6, 2, 2>},
+    {kRlev2Dense8, enqueue<kSer, 8, 6, 2, 0>, nullptr},    // dense-capable, 8.5 KB
+    {kRlev2Dense12, enqueue<kSer, 12, 5, 2, 0>, nullptr},  // dense-capable, 12.5 KB
+    // union, two passes: dense passes table their runs, rlev2_expand_kernel expands them in value slices
+    {kRlev2UnionTwoPass, enqueue<kSer | kOptUnion | kOptTable, 8, 6, 2, 0>, nullptr},
+    // 33 KB serial + dense drain (round-3 default, A/B)
+    {kRlev2WideDrain, enqueue<kWide, 33, 1, 0, 1>, enqueue<kSer, 8, 6, 2, 2>},
+    {kRlev2UnionOnePass, enqueue<kSer | kOptUnion, 8, 6, 2, 0>, nullptr},  // union in one pass (round-5 default)
+    {kRlev2WideNoFlat, enqueue<kWide, 33, 1, 0, 0>, nullptr},            // kRlev2Wide without the flat prologue (A/B control)
+    {kRlev2WideFlat8, enqueue<kWide | kOptFlat, 33, 1, 0, 0>, nullptr},  // kRlev2Wide without kOptFlat16 (A/B control)
+};
+
+// A serial instance that queues its short-run segments, then the dense
+// instance that drains the queue.
+static int launch_deferring(Ctx* ctx, TiledLaunch& l, const Instance& in) {
+  const int rc = defer_queue(ctx, l.a.nsegs, &l.dq);
+  if (rc) return rc;
+  l.dpar = (uint32_t)(ctx->defer_seq++ % 0xffffffffull) + 1u;  // never 0
+  in.launch(ctx, l);
+  debug_defer(ctx, l.dq, l.a.nsegs, l.dpar);
+  in.drain(ctx, l);
+  return ORCG_OK;
+}
+
+// One launch (or serial + drain pair, or two passes) of instance `variant`
+// over the segments of one stream, or (ml) over the launch-wide segments of a
+// planned launch's device job table.
+static int launch_tiled(Ctx* ctx, int variant, const Rlev2Args& a, const MultiLaunch* ml = nullptr) {
+  if (a.nsegs == 0 || a.nvalues == 0) return ORCG_OK;
+  TiledLaunch l{a, nullptr, 0, nullptr, 0, RunTab{nullptr, nullptr, 0, 0}};
+  if (ml) {
+    l.jobs = (const RleJob*)ml->d_jobs;
+    l.njobs = ml->njobs;
   }
-  return launch_tiled(ctx, variant, d_src, src_len, is_signed, d_segtab, nsegs, positions_mode, rows_per_group,
-                      value_begin, nvalues, d_dst, dst_bytes, nullptr, 0, d_count);
+  if (variant == kRlev2UnionTwoPass) {
+    // two passes when the run table can address the launch, else one
+    const uint64_t bound = a.positions ? a.rows_per_group + 512 : seg_value_bound(a.nvalues, a.nsegs);
+    const TwoPass tp = ml ? TwoPass{ml->tab_entries, ml->spg, ml->slice} : stream_two_pass(a.src_len, a.nsegs, bound);
+    if (two_pass_fits(tp.entries, a.nsegs, tp.spg)) {
+      const int rc = runtab_buffers(ctx, tp.entries, a.nsegs, tp.spg, tp.slice, &l.rtab);
+      if (rc) return rc;
+    } else {
+      variant = kRlev2UnionOnePass;
+    }
+  }
+  if (a.nsegs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
+  if (a.dst_bytes != 8 && a.dst_bytes != 4 && a.dst_bytes != 2)
+    return set_error(ctx, ORCG_INVALID_ARGUMENT, "dst_bytes must be 8, 4 or 2");
+  const Instance* in = std::find_if(std::begin(kInstances), std::end(kInstances),
+                                    [&](const Instance& i) { return i.id == variant; });
+  if (in == std::end(kInstances)) return set_error(ctx, ORCG_INVALID_ARGUMENT, "unknown RLEv2 kernel variant");
+  if (in->drain) {
+    const int rc = launch_deferring(ctx, l, *in);
+    if (rc) return rc;
+  } else {
+    in->launch(ctx, l);
+  }
+  const int rc = hip_check(ctx, hipGetLastError(), "rlev2_tiled_kernel launch");
+  if (rc || variant != kRlev2UnionTwoPass) return rc;
+  return launch_rlev2_expand(ctx, a, l.jobs, l.njobs, l.rtab);
+}
+
+int launch_rlev2_tiled(Ctx* ctx, const Rlev2Args& a) {
+  const uint64_t est = a.positions ? a.nsegs * a.rows_per_group : a.nvalues;
+  return launch_tiled(ctx, route_rlev2(Rlev2Route{a.src_len, est, a.nsegs, cu_count(ctx), ctx->rlev2_variant, false}), a);
 }
 
 int launch_rlev2_tiled_jobs(Ctx* ctx, const MultiLaunch& m) {
-  return launch_tiled(ctx, m.variant, nullptr, 0, 0, nullptr, m.grid, false, 0, 0, m.values, nullptr, 8,
-                      (const RleJob*)m.d_jobs, m.njobs, nullptr, &m);
+  Rlev2Args a{};  // the streams are the job table's
+  a.nsegs = m.grid;
+  a.nvalues = m.values;
+  a.dst_bytes = 8;
+  return launch_tiled(ctx, m.variant, a, &m);
 }
-
-bool rlev2_multi_capable(int variant) { return variant == 0 || (variant >= 2 && variant <= 10); }
 
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out) {
   const int pinned = ctx->rlev2_variant;
@@ -2240,47 +2169,25 @@ int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<M
     }
     return ORCG_OK;
   }
-  // one launch per instance: group the streams by the instance they get
-  std::vector<RleJob> group[11];
-  for (uint32_t j = 0; j < njobs; ++j) {
-    const RleJob& J = jobs[j];
-    if (J.nsegs == 0 || J.nvalues == 0) continue;
-    group[pinned ? pinned : default_variant(J.src_len, J.nvalues)].push_back(J);
-  }
+  const int cus = cu_count(ctx);
+  const std::vector<Rlev2Group> groups = group_rlev2_jobs(jobs, njobs, pinned, cus);
   if (debug_on("jobs"))
-    for (int v = 2; v <= 10; ++v)
-      for (const RleJob& J : group[v])
-        fprintf(stderr, "rle job: instance %d bytes %llu values %llu segments %llu (%.3f B/value)\n", v,
-                (unsigned long long)J.src_len, (unsigned long long)J.nvalues, (unsigned long long)J.nsegs,
-                (double)J.src_len / (double)J.nvalues);
-  for (int v = 2; v <= 10; ++v) {
-    std::vector<RleJob>& g = group[v];
-    if (g.empty()) continue;
-    // workgroups start in index order: the streams with the most stream
-    // bytes per value (the most runs per segment, the slowest segments) first,
-    // so the launch does not end on a tail of slow segments
-    std::stable_sort(g.begin(), g.end(), [](const RleJob& a, const RleJob& b) {
-      return (double)a.src_len * (double)b.nvalues > (double)b.src_len * (double)a.nvalues;
-    });
-    uint64_t segs = 0, values = 0, entries = 0, bound = 0;
-    for (RleJob& J : g) {
-      J.seg_base = segs;
-      segs += J.nsegs;
-      values += J.nvalues;
-      // two-pass (the union instance): the job's run-table range
-      J.tab_base = (uint32_t)std::min<uint64_t>(entries, 0xffffffffull);
-      entries += J.src_len / 2 + J.nsegs + 1;
-      bound = std::max(bound, seg_value_bound(J.nvalues, J.nsegs));
-    }
-    if (segs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
+    for (const Rlev2Group& g : groups)
+      for (uint32_t j = 0; j < njobs; ++j)
+        if (rlev2_job_instance(jobs[j], pinned, cus) == g.variant)
+          fprintf(stderr, "rle job: instance %d bytes %llu values %llu segments %llu (%.3f B/value)\n", g.variant,
+                  (unsigned long long)jobs[j].src_len, (unsigned long long)jobs[j].nvalues,
+                  (unsigned long long)jobs[j].nsegs, (double)jobs[j].src_len / (double)jobs[j].nvalues);
+  for (const Rlev2Group& g : groups) {
+    if (g.segs > 0x7fffffffull) return set_error(ctx, ORCG_INVALID_ARGUMENT, "too many segments");
     const RleJob* d = nullptr;
-    const int rc = stage_rle_jobs(ctx, g.data(), (uint32_t)g.size(), &d);
+    const int rc = stage_rle_jobs(ctx, g.jobs.data(), (uint32_t)g.jobs.size(), &d);
     if (rc) return rc;
-    const int lv = (v == 6 && !pinned) ? union_variant(ctx, segs) : v;
-    MultiLaunch m{MultiLaunch::kRlev2, lv, d, (uint32_t)g.size(), segs, values};
-    if (lv == 6 && entries < 0xffff0000ull) {
-      m.tab_entries = entries;
-      two_pass_shape(bound, &m.spg, &m.slice);
+    MultiLaunch m{MultiLaunch::kRlev2, g.launch_variant, d, (uint32_t)g.jobs.size(), g.segs, g.values};
+    if (g.spg) {
+      m.tab_entries = g.entries;
+      m.spg = g.spg;
+      m.slice = g.slice;
     }
     out.push_back(m);
   }

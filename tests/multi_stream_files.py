@@ -297,10 +297,11 @@ def file_s():
     return CraftedFile(M_NAMES, M_KINDS, S_STRIDE, [(S_ROWS, m_columns(seed, S_ROWS)) for seed in S_SEEDS])
 
 
-# ---- the launch planner's rules, restated (rlev2_tiled.hip) ----------------
+# ---- the launch planner's rules, restated (rlev2_route.hh; checked against
+# it by tests/test_cxx_rlev2_route.py) ------------------------------------------
 def density_class(src_len, values):
-    """default_variant: the instance a stream of src_len bytes and `values`
-    values gets (6: the union instance)."""
+    """route_rlev2 for a job of a multi-stream launch: the instance a stream
+    of src_len bytes and `values` values gets (6: the union instance)."""
     return 2 if src_len >= 5 * values else (3 if 4 * src_len >= 5 * values else 6)
 
 

@@ -34,7 +34,7 @@ CONSTANTS = {
                             ORCG_VPAR_MIN=16, kToDense=24, kToSerial=64, ORCG_TAB_TO_DENSE=128,
                             ORCG_TAB_TO_SERIAL=512, ORCG_ITEM_MAX=64),
     "rlev2_expand.hip": dict(kRound=256),
-    "orcg_internal.hh": dict(kSliceMax=1024, kMaxRlev2Variant=10),
+    "rlev2_route.hh": dict(kSliceMax=1024, kMaxRlev2Variant=10),
     "host_plan.hh": dict(kRlev2HdrLim=HDR_LIM),
 }
 _T = CONSTANTS["rlev2_tiled.hip"]
@@ -43,12 +43,12 @@ BLK = SLAB // _T["kThreads"]  # kBlk: bytes a thread owns in dense discovery
 SUPER = 8 * BLK               # kSup
 DENSE_RUNS = SLAB // 2        # kDenseRuns
 SERIAL_RUNS = 512             # kCap of the serial instances
-SLICE_MAX, ROUND = CONSTANTS["orcg_internal.hh"]["kSliceMax"], CONSTANTS["rlev2_expand.hip"]["kRound"]
+SLICE_MAX, ROUND = CONSTANTS["rlev2_route.hh"]["kSliceMax"], CONSTANTS["rlev2_expand.hip"]["kRound"]
 LONGEST_RUN = 4356            # PATCHED W=64 L=512 bw=8, 31 entries of 64 bits
 _WINS = _T["kThreads"] // 64 * _T["kStage"] * 8 + SLAB // 8  # what a union instance's serial window adds
 
 # variant -> (kWin, what walks it, kWinS: the serial window of a union instance)
-# launch_tiled's ORCG_KX lines: kWin = KB * 1024, + 512 in dense-capable instances
+# rlev2_tiled.hip kInstances' rows: kWin = KB * 1024, + 512 in dense-capable instances
 VARIANTS = {
     0: (None, "default", None),  # picks 2, 3, 6 or 8 by the stream's bytes per value
     1: (None, "wave-walk", None),
@@ -938,7 +938,8 @@ def slices():
 
 def two_pass_shape(nvalues, nsegs):
     """(slices a segment, values a slice) of a two-pass launch over a segment
-    table (rlev2_tiled.hip seg_value_bound, two_pass_shape)."""
+    table (rlev2_route.hh seg_value_bound, two_pass_shape; checked against
+    them by tests/test_cxx_rlev2_route.py)."""
     avg = (nvalues + nsegs - 1) // max(nsegs, 1)
     n = max(avg + avg // 8 + 512, 1)
     k = min((n + SLICE_MAX - 1) // SLICE_MAX, 256)

@@ -311,16 +311,20 @@ def test_the_models_constants_are_the_sources():
     assert "avail, kRlev2HdrLim, is_signed)" in open(os.path.join(csrc, "rlev2_expand.hip")).read()
     assert open(os.path.join(csrc, "rlev2_kernels.hip")).read().count("kRlev2HdrLim") >= 3
     assert not re.search(r"parse_run\([^;]*\b64u?,\s*is_signed", "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))))
-    # the instances: `case V: ... (options, window KB, min waves, kDense, ...)`
-    inst = re.findall(r"case (\d+):[^;]*?ORCG_(?:KX|DEFERRING)\([^,]+, (\d+), \d+, (\w+)", text)
-    assert sorted(int(v) for v, _, _ in inst) == list(range(2, 11))
+    # the instances, kInstances' rows: `{id, enqueue<options, window KB, min waves, kDense, kDefer>, drain}`,
+    # the ids by their names in rlev2_route.hh
+    ids = source_constants("rlev2_route.hh")
+    table = text[text.index("constexpr Instance kInstances[] = {"):]
+    inst = re.findall(r"\{(kRlev2\w+), enqueue<[^,]+, (\d+), \d+, (\d+), \d+>, (?:nullptr|enqueue<[^>]*>)\}",
+                      table[:table.index("};")])
+    assert sorted(ids[v] for v, _, _ in inst) == list(range(2, 11))
     for v, kb, dense in inst:
-        v, kb = int(v), int(kb)
+        v, kb = ids[v], int(kb)
         win, kind, wins = m.VARIANTS[v]
         assert win == kb * 1024 + (512 if dense == "2" else 0), v
         assert (kind in ("dense", "union", "two-pass")) == (dense == "2"), v
         assert (wins is not None) == (kind in ("union", "two-pass")) and (wins is None or wins == win + 4 * 256 * 8 + 256)
-    assert sorted(m.VARIANTS) == orc_amd.rlev2_variants() == list(range(m.CONSTANTS["orcg_internal.hh"]["kMaxRlev2Variant"] + 1))
+    assert sorted(m.VARIANTS) == orc_amd.rlev2_variants() == list(range(m.CONSTANTS["rlev2_route.hh"]["kMaxRlev2Variant"] + 1))
     assert m.WINDOWS == [(8704, 8704), (8704, 17152), (12800, 12800), (21504, 21504), (33792, 33792)]
 
 
