@@ -1,7 +1,7 @@
 // The stripe scheduler's host side: the job-table ring / arena (stage_table)
 // and run_multi, which enqueues a batch's planned launches (RLEv2 instances,
 // RLEv1, varint counts, dictionaries, decimals, length scans) over the
-// context's stream and its side lanes.
+// context's stream and its side lanes (forked and joined by LaneFork).
 #include <cstdio>
 #include <cstring>
 
@@ -71,22 +71,14 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
   const bool par = nlanes > 0 && side_lanes() > 1 && (size_t)nlanes <= side_lanes() &&
                    ctx_lane(ctx, (size_t)nlanes - 1) != nullptr;
   Ctx* const base = ctx;
-  int used = 0, aux_lane = -1, rc = ORCG_OK;
-  if (par) rc = hip_check(ctx, hipEventRecord(ctx->ev_fork, ctx->stream), "fork event");
-  auto fork = [&](Ctx** c) -> int {  // the next lane, started after the fork point
-    *c = base->lanes[used++];
-    return hip_check(base, hipStreamWaitEvent((*c)->stream, base->ev_fork, 0), "fork wait");
-  };
-  bool joined = false;
+  LaneFork lf(base);
+  size_t next = 0;         // lanes handed out so far, in launch order
+  Ctx* aux_ctx = nullptr;  // the auxiliary lane
+  bool joined = false;     // past the join: everything runs on base
+  int rc = par ? lf.begin() : ORCG_OK;
   auto join = [&]() -> int {
-    int r = ORCG_OK;
-    for (int k = 0; k < used; ++k) {
-      int jr = hip_check(base, hipEventRecord(base->ev_join[k], base->lanes[k]->stream), "join event");
-      if (!jr) jr = hip_check(base, hipStreamWaitEvent(base->stream, base->ev_join[k], 0), "join wait");
-      if (jr && !r) r = jr;
-    }
     joined = true;
-    return r;
+    return lf.join();
   };
   for (size_t i = 0; i < ls.size() && !rc; ++i) {
     const MultiLaunch& m = ls[i];
@@ -94,13 +86,11 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
     debug_stale("run_multi: before a launch");
     if (m.kind == MultiLaunch::kRlev2) {
       Ctx* c = base;
-      if (par && (int)i != crit && (rc = fork(&c))) break;
+      if (par && (int)i != crit && (rc = lf.lane(next++, &c))) break;
       // jobs without a record of their own report into the base's (the
       // lane's own record is the lane's: it frees it)
-      unsigned long long* const own = c->d_err;
-      c->d_err = base->d_err;
+      const ErrRecordScope err(c, base->d_err);
       rc = launch_rlev2_tiled_jobs(c, m);
-      c->d_err = own;
       if (rc) {
         char b[160];
         snprintf(b, sizeof b, " (instance %d, %u streams, %llu segments%s)", m.variant, m.njobs,
@@ -110,14 +100,10 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
     } else if (on_aux_lane(m.kind)) {
       Ctx* c = base;
       if (par && !joined) {
-        if (aux_lane < 0) {
-          if ((rc = fork(&c))) break;
-          aux_lane = used - 1;
-        }
-        c = base->lanes[aux_lane];
+        if (!aux_ctx && (rc = lf.lane(next++, &aux_ctx))) break;
+        c = aux_ctx;
       }
-      unsigned long long* const own = c->d_err;
-      c->d_err = base->d_err;
+      const ErrRecordScope err(c, base->d_err);
       if (m.kind == MultiLaunch::kRlev1) {
         rc = launch_rlev1_jobs(c, (const V1SegDesc*)m.d_jobs, m.grid, m.variant);
       } else {
@@ -126,7 +112,6 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
         rc = launch_varint_tile_counts(c, J.src, J.len, J.counts, &ntiles);
         if (!rc) rc = launch_exclusive_scan(c, J.counts, ntiles, J.base, nullptr, J.total);
       }
-      c->d_err = own;
       if (rc && c != base) base->last_error = c->last_error;
     } else if (m.kind == MultiLaunch::kDict) {
       rc = launch_dict_jobs(base, (const DictJob*)m.d_jobs, m.njobs, m.grid);
@@ -138,8 +123,7 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
     } else {
       // kRlev2Pinned, a pinned single-stream variant: host job (d_jobs is a host pointer)
       const RleJob& J = *(const RleJob*)m.d_jobs;
-      unsigned long long* const saved = base->d_err;  // the job's own error record
-      if (J.err) base->d_err = J.err;
+      const ErrRecordScope err(base, J.err ? J.err : base->d_err);  // the job's own error record
       Rlev2Args a{};
       a.src = J.src;
       a.src_len = J.src_len;
@@ -150,7 +134,6 @@ int run_multi(Ctx* ctx, const std::vector<MultiLaunch>& ls) {
       a.dst = J.dst;
       a.dst_bytes = 8;
       rc = launch_rlev2(base, a);
-      base->d_err = saved;
     }
   }
   if (!joined) {  // join what was forked (also after a failure)

@@ -87,6 +87,41 @@ Ctx* ctx_lane(Ctx* base, size_t k) {
   if (!l->num_cus) l->num_cus = base->num_cus;
   return l;
 }
+
+int LaneFork::begin() {
+  if (!base->ev_fork && !ctx_lane(base, 0)) return set_error(base, ORCG_DEVICE_ERROR, "side stream creation failed");
+  return hip_check(base, hipEventRecord(base->ev_fork, base->stream), "fork event");
+}
+
+int LaneFork::lane(size_t k, Ctx** out) {
+  Ctx* const l = ctx_lane(base, k);
+  if (!l) return set_error(base, ORCG_DEVICE_ERROR, "side stream creation failed");
+  *out = l;
+  if (used.size() < base->lanes.size()) used.resize(base->lanes.size(), 0);
+  if (used[k]) return ORCG_OK;
+  used[k] = 1;
+  return hip_check(base, hipStreamWaitEvent(l->stream, base->ev_fork, 0), "fork wait");
+}
+
+int LaneFork::chain(size_t from, size_t to) {
+  int rc = hip_check(base, hipEventRecord(base->ev_join[from], base->lanes[from]->stream), "fork event");
+  if (!rc) rc = hip_check(base, hipStreamWaitEvent(base->lanes[to]->stream, base->ev_join[from], 0), "fork wait");
+  if (used.size() < base->lanes.size()) used.resize(base->lanes.size(), 0);
+  if (!rc) used[to] = 1;
+  return rc;
+}
+
+int LaneFork::join() {
+  int rc = ORCG_OK;
+  for (size_t k = 0; k < used.size(); ++k) {
+    if (!used[k]) continue;
+    int jr = hip_check(base, hipEventRecord(base->ev_join[k], base->lanes[k]->stream), "join event");
+    if (!jr) jr = hip_check(base, hipStreamWaitEvent(base->stream, base->ev_join[k], 0), "join wait");
+    if (jr && !rc) rc = jr;
+  }
+  used.clear();
+  return rc;
+}
 }  // namespace orcg
 
 using namespace orcg;

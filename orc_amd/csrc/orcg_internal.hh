@@ -77,7 +77,8 @@ struct Ctx {
   uint64_t arena_cap = 0, arena_used = 0;
   // side contexts (own stream, scratch, queues) the file reader decodes
   // sibling column subtrees on concurrently, forked from and joined back into
-  // this context's stream with events; created on first use (ctx_lane)
+  // this context's stream with events (LaneFork); created on first use
+  // (ctx_lane)
   std::vector<Ctx*> lanes;
   hipEvent_t ev_fork = nullptr;
   std::vector<hipEvent_t> ev_join;
@@ -86,6 +87,38 @@ struct Ctx {
 // Side context k of `base` (created on first use, settings copied from base);
 // nullptr if it cannot be created.
 Ctx* ctx_lane(Ctx* base, size_t k);
+
+// One fork of `base`'s stream over its side lanes: which lanes were started
+// from the fork point and have to be joined back. The callers (run_multi, the
+// struct's fork, the pre-loaded dictionaries' lane) decide what runs where.
+// Every member returns a hip_check status, its message in base->last_error.
+struct LaneFork {
+  explicit LaneFork(Ctx* b) : base(b) {}
+  // the fork point: base->ev_fork on base's stream
+  int begin();
+  // *out = side lane k, made to wait for the fork point the first time k is
+  // handed out (ORCG_DEVICE_ERROR: the lane could not be created)
+  int lane(size_t k, Ctx** out);
+  // lane `to` continues after what lane `from` holds now (and is joined too)
+  int chain(size_t from, size_t to);
+  // base's stream waits for every lane handed out since the last join: all
+  // of them are tried, the first failure is returned; a second call is a no-op
+  int join();
+
+ private:
+  Ctx* const base;
+  std::vector<uint8_t> used;  // per lane: started from the fork point, not joined yet
+};
+
+// Redirects a context's device error record for a scope (a column's own
+// record, a job's, the base's for a lane that runs the base's jobs)
+struct ErrRecordScope {
+  Ctx* const ctx;
+  unsigned long long* const saved;
+  ErrRecordScope(Ctx* c, unsigned long long* rec) : ctx(c), saved(c->d_err) { c->d_err = rec; }
+  ~ErrRecordScope() { ctx->d_err = saved; }
+};
+
 // One no-op launch per kernel file on `s`: HIP loads a file's code object at
 // its first launch (tens of ms for all of them), so the first context of a
 // process pays it at creation instead of inside its first decode

@@ -3,7 +3,7 @@
 // counts the host knows are queued for one launch per kernel instance.
 #include "reader_internal.hh"
 
-int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t count) {
+int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, const Rows& r, uint64_t count) {
   Col& c = H->cols[id];
   const int slot = desc.slot;
   const bool is_signed = desc.is_signed;
@@ -14,7 +14,7 @@ int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t coun
   const bool v1 = rle_v1(c.encoding, desc.force_v2);
   if (!sb.pos && count > sb.plan->values) return ORCG_OK;
   // (collect() runs before the stripe's upload: no device work here)
-  if (sb.pos && !(cur_rows && (v1 || rlev2_multi_capable(act.ctx->rlev2_variant)))) return ORCG_OK;
+  if (sb.pos && !(r.rg_rows && (v1 || rlev2_multi_capable(act.ctx->rlev2_variant)))) return ORCG_OK;
   if (v1) {
     // RLEv1: one host-built descriptor per segment (the plan's cuts, or the
     // row index with the stripe's row-group starts g * stride)
@@ -55,12 +55,12 @@ int orcg_reader::queue_stream(uint32_t id, const StreamDesc& desc, uint64_t coun
     // the row index is the segment table (no rg_segtab launch): collect()
     // only queues columns whose rows are all values (no mask)
     j.trip = (const int64_t*)(D->d_stage + sb.rg_off);
-    j.rows = cur_rows;
+    j.rows = r.rg_rows;
     j.nsegs = H->ngroups;
   } else {
     const uint64_t* d_seg;
     uint64_t nseg;
-    int rc = segments(c, slot, false, &d_seg, &nseg);
+    int rc = segments(c, slot, false, r, &d_seg, &nseg);
     if (rc) return rc;
     j.segtab = d_seg;
     j.nsegs = nseg;
@@ -189,7 +189,11 @@ int orcg_reader::collect_dicts(uint32_t id) {
   if (is_string_kind(k) && is_dict(c.encoding)) {
     const uint64_t D_ = c.dict_size;
     if (D_ == 0 || D_ > kDictLds || !c.s[kSlotLength].present) return ORCG_OK;
-    int rc = queue_stream(id, *layout(id, c).find(kSlotLength), D_);
+    // (no row groups: a dictionary's LENGTH stream holds an entry per
+    // dictionary entry, count == kDictSize, which reader_layout.hh never
+    // positions by the row index, so the rows' row groups are never read)
+    const Rows entries{D_, D_, nullptr, nullptr, nullptr, nullptr};
+    int rc = queue_stream(id, *layout(id, c).find(kSlotLength), entries, D_);
     if (rc) return rc;
     const StripeBatch::Values* li = B.find(id, kSlotLength);
     if (!li || li->count != D_) return ORCG_OK;
@@ -210,15 +214,12 @@ int orcg_reader::collect(uint32_t id, uint64_t n, const int64_t* rg_rows) {
   Col& c = H->cols[id];
   if (!act.selected[id] || !c.supported) return ORCG_OK;
   if (c.s[kSlotPresent].present) return collect_dicts(id);  // its counts come from the device
-  cur_rows = rg_rows;
-  cur_n = n;
-  cur_in_nn = nullptr;
-  cur_row_nn = nullptr;
+  const Rows r{n, n, nullptr, nullptr, rg_rows, nullptr};  // no masks: every row holds a value
   const uint32_t k = c.kind;
   const StreamLayout lay = layout(id, c);
   int rc = ORCG_OK;
   for (const StreamDesc& d : lay)
-    if (!rc && d.coding == kIntRle) rc = queue_stream(id, d, d.count == kDictSize ? c.dict_size : n);
+    if (!rc && d.coding == kIntRle) rc = queue_stream(id, d, r, d.count == kDictSize ? c.dict_size : n);
   if (rc) return rc;
   const StreamDesc* data = lay.find(kSlotData);
   if (data && data->coding == kVarint) {  // decimals

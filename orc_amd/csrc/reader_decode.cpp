@@ -10,26 +10,13 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
   Col& c = H->cols[id];
   if (!act.selected[id] || !c.supported) return ORCG_OK;
   // this column's kernels report into its own device error record
-  struct Scope {
-    orcg_reader* r;
-    uint32_t col;
-    unsigned long long* err;
-    ~Scope() {
-      r->cur_col = col;
-      r->act.ctx->d_err = err;
-    }
-  } scope{this, cur_col, act.ctx->d_err};
-  cur_col = id;
-  act.ctx->d_err = D->d_errs + id;
+  const Restore<uint32_t> col_scope(cur_col, id);
+  const ErrRecordScope err_scope(act.ctx, D->d_errs + id);
   c.n = n;
   c.decoded = true;
   if (!c.stream_err.empty()) return fail(ORCG_PARSE_ERROR, c.stream_err);
-  cur_rows = rg_rows;
-  cur_n = n;
-  cur_in_nn = in_nn;
-  cur_row_nn = nullptr;
-  Rows r{n, 0, nullptr, nullptr, rg_rows};
-  const int rc = decode_present(c, n, in_nn, in_count, d_in_count, in_col, &r);
+  Rows r{n, 0, nullptr, nullptr, rg_rows, in_nn};
+  const int rc = decode_present(c, in_count, d_in_count, in_col, &r);
   if (rc) return rc;
   const StreamLayout lay = layout(id, c);
   const uint32_t k = c.kind;
@@ -52,9 +39,10 @@ int orcg_reader::decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t 
 
 // ColumnReader::next: PRESENT bits for the incoming non-null rows
 // (d_in: their count is on the device, in_count an upper bound)
-int orcg_reader::decode_present(Col& c, uint64_t n, const uint8_t* in_nn, uint64_t in_count,
-                                const uint64_t* d_in_count, Col* in_col, Rows* rows) {
+int orcg_reader::decode_present(Col& c, uint64_t in_count, const uint64_t* d_in_count, Col* in_col, Rows* rows) {
   const uint32_t id = cur_col;
+  const uint64_t n = rows->n;
+  const uint8_t* const in_nn = rows->in_nn;
   const bool has_present = c.s[kSlotPresent].present;
   int rc;
   const bool dev = device_counts(id);
@@ -71,7 +59,7 @@ int orcg_reader::decode_present(Col& c, uint64_t n, const uint8_t* in_nn, uint64
     // the decode counts the set rows it writes: the non-null rows, with or
     // without the parent's mask scattered in
     uint64_t* ones = D->d_ones + id;
-    if ((rc = byte_stream(c, *layout(id, c).find(kSlotPresent), in_nn ? in_count : n, bits, ones, d_in))) return rc;
+    if ((rc = byte_stream(c, *layout(id, c).find(kSlotPresent), *rows, in_nn ? in_count : n, bits, ones, d_in))) return rc;
     if (in_nn) {
       ORCG_ALLOC_TO(uint8_t, nn, n);
       if ((rc = scatter(bits, in_nn, n, nn, 1))) return fail_ctx(rc);
@@ -119,22 +107,21 @@ int orcg_reader::decode_present(Col& c, uint64_t n, const uint8_t* in_nn, uint64
   rows->nonnull = nonnull;
   rows->d_nonnull = d_nonnull;
   rows->row_nn = c.nn;
-  cur_row_nn = c.nn;
   return ORCG_OK;
 }
 
 int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, const Rows& r) {
   const file::TypeInfo& t = footer.types[id];
   const std::string cid = std::to_string(id);
-  const uint64_t n = r.n, nonnull = r.nonnull;
+  const uint64_t nonnull = r.nonnull;
   const bool has_data = c.s[kSlotData].present;
   int rc;
   if (decimal64_v2(t, decimal_as_long)) {
     // Decimal64ColumnReaderV2 (ColumnReader.cc:1529-1576): RLEv2 unscaled values
     if (!has_data) return fail(ORCG_PARSE_ERROR, "DATA stream not found in Decimal64V2 column. ColumnId=" + cid);
     int64_t* dense;
-    if ((rc = int_stream(c, *lay.find(kSlotData), nonnull, &dense))) return rc;
-    return place(dense, 8, n, &c.data);
+    if ((rc = int_stream(c, *lay.find(kSlotData), r, nonnull, &dense))) return rc;
+    return place(dense, 8, r, &c.data);
   }
   // Decimal64ColumnReader / Decimal128ColumnReader (:1384-1527): varint
   // DATA, per-value scales in SECONDARY (signed RLE)
@@ -144,7 +131,7 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
   const bool hive11 = t.precision == 0;
   const bool wide = hive11 || t.precision > 18;
   int64_t* scales;
-  if ((rc = int_stream(c, *lay.find(kSlotSecondary), nonnull, &scales))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotSecondary), r, nonnull, &scales))) return rc;
   const StreamBuf& sb = c.s[kSlotData];
   const uint8_t* d_src = D->d_stage + sb.host_off;
   int64_t* base = nullptr;
@@ -187,7 +174,7 @@ int orcg_reader::decode_decimal(uint32_t id, Col& c, const StreamLayout& lay, co
                                   hive11 ? hive11_scale : (int32_t)t.scale, hive11 ? (nullify ? 3 : 2) : (wide ? 1 : 0),
                                   dense, keep)))
     return fail_ctx(rc);
-  if ((rc = place(dense, wide ? 16 : 8, n, &c.data))) return rc;
+  if ((rc = place(dense, wide ? 16 : 8, r, &c.data))) return rc;
   return nullify && nonnull ? decode_hive11_nulls(c, keep, r) : ORCG_OK;
 }
 
@@ -198,7 +185,7 @@ int orcg_reader::decode_hive11_nulls(Col& c, const uint8_t* keep, const Rows& r)
   const uint64_t n = r.n;
   int rc;
   const uint8_t* rnn;
-  if ((rc = place(keep, 1, n + 8, &rnn))) return rc;
+  if ((rc = place(keep, 1, r, &rnn, 8))) return rc;  // (the 8 bytes of padding `keep` has)
   // the column's own count word: sibling decimal columns decode on other
   // side lanes concurrently
   const uint64_t* h_kept = nullptr;
@@ -304,8 +291,8 @@ int orcg_reader::decode_timestamp(Col& c, const StreamLayout& lay, const Rows& r
   if (!c.s[kSlotSecondary].present) return fail(ORCG_PARSE_ERROR, "SECONDARY stream not found in Timestamp column");
   int rc;
   int64_t *secs, *nanos;
-  if ((rc = int_stream(c, *lay.find(kSlotData), r.nonnull, &secs, r.d_nonnull))) return rc;
-  if ((rc = int_stream(c, *lay.find(kSlotSecondary), r.nonnull, &nanos, r.d_nonnull))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotData), r, r.nonnull, &secs, r.d_nonnull))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotSecondary), r, r.nonnull, &nanos, r.d_nonnull))) return rc;
   // TIMESTAMP_INSTANT ignores both zones; the same zone on both sides is
   // sameTimezone_ (:286): no adjustment, with that zone's epoch
   const ZoneEntry* wz = c.kind == ORCG_TYPE_TIMESTAMP ? H->writer_zone : nullptr;
@@ -319,15 +306,15 @@ int orcg_reader::decode_timestamp(Col& c, const StreamLayout& lay, const Rows& r
     if ((rc = zone_table(wz, &wt)) || (rc = zone_table(act.reader_tz, &rt))) return rc;
     if ((rc = launch_timestamp_tz(act.ctx, secs, nanos, r.nonnull, wt, rt))) return fail_ctx(rc);
   }
-  if ((rc = place(secs, 8, r.n, &c.data))) return rc;
-  return place(nanos, 8, r.n, &c.secondary);
+  if ((rc = place(secs, 8, r, &c.data))) return rc;
+  return place(nanos, 8, r, &c.secondary);
 }
 
 int orcg_reader::decode_integer(Col& c, const StreamLayout& lay, const Rows& r) {
   if (!c.s[kSlotData].present) return fail(ORCG_PARSE_ERROR, "DATA stream not found in Integer column");
   int64_t* dense;
-  const int rc = int_stream(c, *lay.find(kSlotData), r.nonnull, &dense, r.d_nonnull);
-  return rc ? rc : place(dense, 8, r.n, &c.data);
+  const int rc = int_stream(c, *lay.find(kSlotData), r, r.nonnull, &dense, r.d_nonnull);
+  return rc ? rc : place(dense, 8, r, &c.data);
 }
 
 int orcg_reader::decode_bytes(Col& c, const StreamLayout& lay, const Rows& r) {
@@ -337,10 +324,10 @@ int orcg_reader::decode_bytes(Col& c, const StreamLayout& lay, const Rows& r) {
                                           : "DATA stream not found in Byte column");
   int rc;
   ORCG_ALLOC(uint8_t, bytes, r.nonnull + 8);
-  if ((rc = byte_stream(c, *lay.find(kSlotData), r.nonnull, bytes))) return rc;
+  if ((rc = byte_stream(c, *lay.find(kSlotData), r, r.nonnull, bytes))) return rc;
   ORCG_ALLOC(int64_t, dense, r.nonnull);
   if ((rc = launch_widen(act.ctx, bytes, boolean ? kWidenU8 : kWidenI8, r.nonnull, dense))) return fail_ctx(rc);
-  return place(dense, 8, r.n, &c.data);
+  return place(dense, 8, r, &c.data);
 }
 
 int orcg_reader::decode_double(Col& c, const Rows& r) {
@@ -357,7 +344,7 @@ int orcg_reader::decode_double(Col& c, const Rows& r) {
   } else {
     dense = (double*)raw;  // zero copy: the stream bytes are the values
   }
-  return place(dense, 8, r.n, &c.data);
+  return place(dense, 8, r, &c.data);
 }
 
 void orcg_reader::check_dictionary(uint32_t id, Col& c, const uint64_t* h) {
@@ -415,7 +402,7 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
   } else {
     int64_t* dlen;
     ORCG_ALLOC_TO(int64_t, doff, dict_size + 1);
-    if ((rc = int_stream(c, *lay.find(kSlotLength), dict_size, &dlen))) return rc;
+    if ((rc = int_stream(c, *lay.find(kSlotLength), r, dict_size, &dlen))) return rc;
     const uint64_t* h_sum = nullptr;
     uint64_t* summary = rb_alloc(2, &h_sum);  // blob bytes, negative-length flag
     if (!summary) ORCG_ALLOC_TO(uint64_t, summary, 2);
@@ -436,8 +423,8 @@ int orcg_reader::decode_dict_string(uint32_t id, Col& c, const StreamLayout& lay
   check_dictionary(id, c, h);
   if (!c.s[kSlotData].present) return fail(ORCG_PARSE_ERROR, "DATA stream not found in StringDictionaryColumn");
   int64_t *idx, *ridx;
-  if ((rc = int_stream(c, *lay.find(kSlotData), r.nonnull, &idx, r.d_nonnull))) return rc;
-  if ((rc = place(idx, 8, n, &ridx))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotData), r, r.nonnull, &idx, r.d_nonnull))) return rc;
+  if ((rc = place(idx, 8, r, &ridx))) return rc;
   c.index = ridx;
   c.dict_offsets = doff;
   if (!act.lazy_dict) {
@@ -459,7 +446,7 @@ int orcg_reader::decode_direct_string(uint32_t id, Col& c, const StreamLayout& l
   if (!c.s[kSlotData].present) return fail(ORCG_PARSE_ERROR, "DATA stream not found in StringDirectColumn");
   int rc;
   int64_t* dlen;
-  if ((rc = int_stream(c, *lay.find(kSlotLength), r.nonnull, &dlen))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotLength), r, r.nonnull, &dlen))) return rc;
   const uint64_t ns = r.nonnull;
   // computeSize's checks (ColumnReader.cc:694-710) ride the scan: a
   // negative length, the total's overflow (then the blob's size below),
@@ -501,8 +488,8 @@ int orcg_reader::decode_direct_string(uint32_t id, Col& c, const StreamLayout& l
                   "String length overflow in StringDirectColumnReader for column " + std::to_string(col_id));
     return *need > blob_len ? fail(ORCG_PARSE_ERROR, "failed to read in StringDirectColumnReader.next") : ORCG_OK;
   });
-  if ((rc = place(dstart, 8, r.n, &c.data))) return rc;
-  return place(dlen, 8, r.n, &c.length);
+  if ((rc = place(dstart, 8, r, &c.data))) return rc;
+  return place(dlen, 8, r, &c.length);
 }
 
 int orcg_reader::decode_list(uint32_t id, Col& c, const StreamLayout& lay, const Rows& r) {
@@ -512,8 +499,8 @@ int orcg_reader::decode_list(uint32_t id, Col& c, const StreamLayout& lay, const
                                                            : "LENGTH stream not found in Map column");
   int rc;
   int64_t *dlen, *rlen;
-  if ((rc = int_stream(c, *lay.find(kSlotLength), r.nonnull, &dlen, r.d_nonnull))) return rc;
-  if ((rc = place(dlen, 8, n, &rlen))) return rc;
+  if ((rc = int_stream(c, *lay.find(kSlotLength), r, r.nonnull, &dlen, r.d_nonnull))) return rc;
+  if ((rc = place(dlen, 8, r, &rlen))) return rc;
   ORCG_ALLOC(int64_t, off, n + 1);
   if ((rc = launch_exclusive_scan(act.ctx, rlen, n, off))) return fail_ctx(rc);
   c.offsets = off;
@@ -547,7 +534,7 @@ int orcg_reader::decode_union(uint32_t id, Col& c, const StreamLayout& lay, cons
   const std::vector<uint32_t> subs = footer.types[id].subtypes;
   const uint32_t nch = (uint32_t)subs.size();
   ORCG_ALLOC(uint8_t, dtags, nonnull + 8);
-  if ((rc = byte_stream(c, *lay.find(kSlotData), nonnull, dtags))) return rc;
+  if ((rc = byte_stream(c, *lay.find(kSlotData), r, nonnull, dtags))) return rc;
   ORCG_ALLOC(uint64_t, bad, 1);
   if ((rc = launch_union_check(act.ctx, dtags, nonnull, nch, bad))) return fail_ctx(rc);
   ORCG_ALLOC(int64_t, doffs, nonnull);
@@ -577,7 +564,7 @@ int orcg_reader::decode_union(uint32_t id, Col& c, const StreamLayout& lay, cons
   if (first_bad != ~0ull)
     return fail(ORCG_PARSE_ERROR, "Invalid union tag " + std::to_string(first_bad & 0xff) + " for union with " +
                                       std::to_string(nch) + " children");
-  if ((rc = place(dtags, 1, n, &c.tags)) || (rc = place(doffs, 8, n, &c.offsets))) return rc;
+  if ((rc = place(dtags, 1, r, &c.tags)) || (rc = place(doffs, 8, r, &c.offsets))) return rc;
   for (uint32_t kk = 0; kk < nch; ++kk) {
     int64_t* child_rows = nullptr;
     if (dense_rows && H->ngroups) {

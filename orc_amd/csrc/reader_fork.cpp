@@ -1,5 +1,6 @@
 // Struct columns: their fields one after the other, or (two or more subtrees
-// with launches of their own) forked over the context's side lanes.
+// with launches of their own) forked over the context's side lanes (LaneFork
+// does the events; what runs on which lane is decided here).
 #include "reader_internal.hh"
 
 int orcg_reader::decode_struct(uint32_t id, Col& c, const Rows& r) {
@@ -23,42 +24,27 @@ int orcg_reader::decode_struct(uint32_t id, Col& c, const Rows& r) {
 // Sibling subtrees on side streams (their kernels run concurrently: most
 // launches of a stripe are one workgroup per row group, a fraction of the
 // chip), forked after this column's work and joined back before anything
-// reads their outputs
+// reads their outputs (LaneFork: kid j on lane j % nl)
 int orcg_reader::fork_struct(Col& c, const std::vector<uint32_t>& kids, unsigned nl, const Rows& r) {
   int rc = ORCG_OK;
   Ctx* base = act.ctx;
   if (!ctx_lane(base, 0)) return fail(ORCG_DEVICE_ERROR, "side stream creation failed");
-  if ((rc = hip_check(act.ctx, hipEventRecord(base->ev_fork, base->stream), "fork event"))) return fail_ctx(rc);
-  std::vector<uint8_t> used(nl, 0);
+  LaneFork lf(base);
+  if ((rc = lf.begin())) return fail_ctx(rc);
   std::vector<Pending> level;  // lists / maps whose children wait for their element counts
-  pending = &level;
+  const Restore<std::vector<Pending>*> pending_scope(pending, &level);
   for (size_t j = 0; j < kids.size() && !rc; ++j) {
-    Ctx* L = ctx_lane(base, j % nl);
-    if (!L) {
-      rc = fail(ORCG_DEVICE_ERROR, "side stream creation failed");
+    Ctx* L = nullptr;
+    if ((rc = lf.lane(j % nl, &L))) {
+      rc = fail_ctx(rc);
       break;
     }
-    if (!used[j % nl]) {
-      used[j % nl] = 1;
-      if ((rc = hip_check(base, hipStreamWaitEvent(L->stream, base->ev_fork, 0), "fork wait"))) {
-        rc = fail_ctx(rc);
-        break;
-      }
-    }
-    act.ctx = L;
-    in_lane = true;
+    const OnLane on_lane(this, L);
     rc = decode(kids[j], r.n, c.nn, r.nonnull, r.rg_rows, c.nn ? r.d_nonnull : nullptr, &c);
-    in_lane = false;
-    act.ctx = base;
   }
-  rc = fork_levels(base, nl, used, level, rc);
-  pending = nullptr;
-  for (unsigned l = 0; l < nl; ++l) {
-    if (!used[l]) continue;
-    int jr = hip_check(base, hipEventRecord(base->ev_join[l], base->lanes[l]->stream), "join event");
-    if (!jr) jr = hip_check(base, hipStreamWaitEvent(base->stream, base->ev_join[l], 0), "join wait");
-    if (jr && !rc) rc = fail_ctx(jr);
-  }
+  rc = fork_levels(lf, base, nl, level, rc);
+  const int jr = lf.join();
+  if (jr && !rc) rc = fail_ctx(jr);
   return rc;
 }
 
@@ -70,8 +56,7 @@ int orcg_reader::fork_struct(Col& c, const std::vector<uint32_t>& kids, unsigned
 // before it go on (their device errors would come first), the earliest
 // column's failure is the one reported, and a level below keeps only the
 // subtrees before it.
-int orcg_reader::fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used, std::vector<Pending>& level,
-                             int rc) {
+int orcg_reader::fork_levels(LaneFork& lf, Ctx* base, unsigned nl, std::vector<Pending>& level, int rc) {
   const int fork_rc = rc;
   const uint32_t fork_col = err_col;
   const std::string fork_msg = last_error;
@@ -117,25 +102,18 @@ int orcg_reader::fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used,
       while (li < nl && base->lanes[li] != cur[q].lane) ++li;
       if (subs.size() == 2 && nl >= 2 && li < nl && device_work(subs[0]) && device_work(subs[1])) {
         const size_t alt = (li + 1) % nl;
-        Ctx* const L2 = base->lanes[alt];
-        hard = hip_check(base, hipEventRecord(base->ev_join[li], cur[q].lane->stream), "fork event");
-        if (!hard) hard = hip_check(base, hipStreamWaitEvent(L2->stream, base->ev_join[li], 0), "fork wait");
-        if (hard) {
+        if ((hard = lf.chain(li, alt))) {
           hard = fail_ctx(hard);
           break;
         }
-        used[alt] = 1;
-        on[1] = L2;
+        on[1] = base->lanes[alt];
       }
-      in_lane = true;
       err_col = kNoCol;
       int lr = ORCG_OK;
       for (size_t si = 0; si < subs.size() && !lr; ++si) {
-        act.ctx = on[si];
+        const OnLane on_lane(this, on[si]);
         lr = decode(subs[si], totals[q], nullptr, totals[q], cur[q].child_rows);
       }
-      in_lane = false;
-      act.ctx = base;
       if (lr) {
         const uint32_t ec = err_col != kNoCol ? err_col : cur[q].id;
         if (ec < fail_col) {

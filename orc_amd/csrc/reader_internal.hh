@@ -519,7 +519,7 @@ struct orcg_reader {
   std::string software_version;  // orcg_reader_software_version's buffer
   std::vector<std::unique_ptr<DevSlot>> slots;  // results of the last read, in stripe order
   size_t nslots = 0;
-  // decode() state: the host stage and device slot of the stripe being decoded
+  // decode() state: the host stage and device slot of the stripe being decoded (Bound)
   HostStage* H = nullptr;
   DevSlot* D = nullptr;
   double timings[5] = {0, 0, 0, 0, 0};
@@ -612,6 +612,20 @@ struct orcg_reader {
   };
   Flight flights[2];
   Flight* F = &flights[0];
+  // a member set for a scope, then put back
+  template <typename T>
+  struct Restore {
+    T& ref;
+    const T old;
+    Restore(T& v, T now) : ref(v), old(v) { ref = now; }
+    ~Restore() { ref = old; }
+  };
+  // issue() and finish(): the flight, and for their scope its stage and slot
+  struct Bound {
+    Restore<HostStage*> h;
+    Restore<DevSlot*> d;
+    Bound(orcg_reader* r, Flight& fl, HostStage* hs, DevSlot* ds) : h(r->H, hs), d(r->D, ds) { r->F = &fl; }
+  };
   // the column decode() is working on, and the column of the first inline
   // (host-detected) failure of this stripe
   static constexpr uint32_t kNoCol = 0xffffffffu;
@@ -716,18 +730,21 @@ struct orcg_reader {
   // mask in_nn is
   int decode(uint32_t id, uint64_t n, const uint8_t* in_nn, uint64_t in_count, const int64_t* rg_rows,
              const uint64_t* d_in_count = nullptr, Col* in_col = nullptr);
-  // The rows of the column being decoded, after its PRESENT stream and the
-  // parent's mask: n rows, of which nonnull hold a value (exact, or with
-  // d_nonnull an upper bound whose exact count is on the device); row_nn: the
-  // column's mask (null: every row holds a value)
+  // The column a decode works on, handed down to every step that needs it:
+  // n rows under the parent's mask in_nn (null: none), of which, after the
+  // column's PRESENT stream, nonnull hold a value (exact, or with d_nonnull
+  // an upper bound whose exact count is on the device); row_nn: the column's
+  // own mask (null: every row holds a value); rg_rows (device, may be null):
+  // the first row of each row group, in the column's rows
   struct Rows {
     uint64_t n, nonnull;
     const uint64_t* d_nonnull;
     const uint8_t* row_nn;
     const int64_t* rg_rows;
+    const uint8_t* in_nn;
   };
-  int decode_present(Col& c, uint64_t n, const uint8_t* in_nn, uint64_t in_count, const uint64_t* d_in_count,
-                     Col* in_col, Rows* rows);
+  // fills nonnull, d_nonnull and row_nn (in_count: the rows set in in_nn)
+  int decode_present(Col& c, uint64_t in_count, const uint64_t* d_in_count, Col* in_col, Rows* rows);
   StreamLayout layout(uint32_t id, const Col& c) const {
     return stream_layout(footer.types[id], c.encoding, decimal_as_long, c.s[kSlotPresent].present);
   }
@@ -761,6 +778,12 @@ struct orcg_reader {
   // Side streams for sibling subtrees (ORCG_LANES, default 4; 1 = one
   // stream). in_lane: decode() runs on a side context (no nested forks).
   bool in_lane = false;
+  // decode() on side context `lane` for a scope
+  struct OnLane {
+    Restore<Ctx*> ctx;
+    Restore<bool> lane;
+    OnLane(orcg_reader* r, Ctx* l) : ctx(r->act.ctx, l), lane(r->in_lane, true) {}
+  };
   // A list / map decoded under a fork whose children wait for its element
   // count (offsets[n] on the device), decoded on the same side context.
   struct Pending {
@@ -770,20 +793,16 @@ struct orcg_reader {
     Ctx* lane;
   };
   std::vector<Pending>* pending = nullptr;
-  int fork_levels(Ctx* base, unsigned nl, std::vector<uint8_t>& used, std::vector<Pending>& level, int rc);
+  int fork_levels(LaneFork& lf, Ctx* base, unsigned nl, std::vector<Pending>& level, int rc);
   static unsigned num_lanes() { return side_lanes(); }
-  // row-group context of the column being decoded (segments())
-  const int64_t* cur_rows = nullptr;  // device: first row of each row group, in the column's rows
-  uint64_t cur_n = 0;
-  const uint8_t* cur_in_nn = nullptr;
-  const uint8_t* cur_row_nn = nullptr;
-  int segments(Col& c, int slot, bool boolean, const uint64_t** d_seg, uint64_t* nseg);
+  int segments(Col& c, int slot, bool boolean, const Rows& r, const uint64_t** d_seg, uint64_t* nseg);
   // RLE integer stream (slot, signedness and RLE version from the column's
   // layout, rle_v1)
   // (*out: the stream's values, decoded by this stripe's multi-stream batch
   // when collect() queued it, else allocated and decoded now)
   // (dcount: the value count on the device, `count` then only sizes the output)
-  int int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t** out, const uint64_t* dcount = nullptr);
+  int int_stream(Col& c, const StreamDesc& d, const Rows& r, uint64_t count, int64_t** out,
+                 const uint64_t* dcount = nullptr);
   // The stripe's multi-stream batch (StripeBatch): collect() queues what
   // the host can count before the upload, plan_batch() turns the queues into
   // launches, and decode() then finds the outputs in B.
@@ -791,7 +810,7 @@ struct orcg_reader {
   StripeBatch B;
   int collect(uint32_t id, uint64_t n, const int64_t* rg_rows);
   int collect_dicts(uint32_t id);
-  int queue_stream(uint32_t id, const StreamDesc& d, uint64_t count);
+  int queue_stream(uint32_t id, const StreamDesc& d, const Rows& r, uint64_t count);
   int queue_dict(uint32_t id, uint64_t n);
   int queue_varint(uint32_t id);
   int queue_decimal(uint32_t id, uint64_t n);
@@ -802,17 +821,17 @@ struct orcg_reader {
   int push_dict(uint32_t id, const int64_t* lengths, const int64_t* idx, uint64_t n, bool gather,
                 std::unordered_map<uint32_t, StripeBatch::DictDone>& done);
   int plan_batch();
-  int byte_stream(Col& c, const StreamDesc& d, uint64_t count, uint8_t* out, uint64_t* d_ones = nullptr,
+  int byte_stream(Col& c, const StreamDesc& d, const Rows& r, uint64_t count, uint8_t* out, uint64_t* d_ones = nullptr,
                   const uint64_t* d_count = nullptr);
   int scatter(const void* dense, const uint8_t* nn, uint64_t n, void* out, int width);
   // Dense values to rows: `dense` itself when the column has no mask, else
-  // `count` elements of `width` bytes with the values scattered to the
-  // column's non-null rows (cur_row_nn, cur_n: the column being decoded)
-  int place_bytes(const void* dense, int width, uint64_t count, void** out);
+  // r.n (+ pad) elements of `width` bytes with the values scattered to the
+  // column's non-null rows
+  int place_bytes(const void* dense, int width, const Rows& r, uint64_t pad, void** out);
   template <typename T, typename U>
-  int place(T* dense, int width, uint64_t count, U** out) {
+  int place(T* dense, int width, const Rows& r, U** out, uint64_t pad = 0) {
     void* p = nullptr;
-    const int rc = place_bytes(dense, width, count, &p);
+    const int rc = place_bytes(dense, width, r, pad, &p);
     *out = (U*)p;
     return rc;
   }

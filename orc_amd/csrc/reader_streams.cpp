@@ -6,18 +6,18 @@ int orcg_reader::scatter(const void* dense, const uint8_t* nn, uint64_t n, void*
   return launch_scatter(act.ctx, dense, nn, n, out, width, 1, 0);
 }
 
-int orcg_reader::place_bytes(const void* dense, int width, uint64_t count, void** out) {
+int orcg_reader::place_bytes(const void* dense, int width, const Rows& r, uint64_t pad, void** out) {
   *out = const_cast<void*>(dense);
-  if (!cur_row_nn) return ORCG_OK;
-  ORCG_ALLOC_TO(uint8_t, *out, count * (uint64_t)width);
-  const int rc = scatter(dense, cur_row_nn, cur_n, *out, width);
+  if (!r.row_nn) return ORCG_OK;
+  ORCG_ALLOC_TO(uint8_t, *out, (r.n + pad) * (uint64_t)width);
+  const int rc = scatter(dense, r.row_nn, r.n, *out, width);
   return rc ? fail_ctx(rc) : ORCG_OK;
 }
 
 // The stream's segment table: the host plan's, or (row-index streams) built
 // on the device from the row groups' positions and the present-row prefix
 // at each row group's first row (PRESENT streams count the incoming rows).
-int orcg_reader::segments(Col& c, int slot, bool boolean, const uint64_t** d_seg, uint64_t* nseg) {
+int orcg_reader::segments(Col& c, int slot, bool boolean, const Rows& r, const uint64_t** d_seg, uint64_t* nseg) {
   StreamBuf& sb = c.s[slot];
   if (!sb.pos) {
     *d_seg = (const uint64_t*)(D->d_stage + sb.seg_off);
@@ -25,23 +25,22 @@ int orcg_reader::segments(Col& c, int slot, bool boolean, const uint64_t** d_seg
     return ORCG_OK;
   }
   const uint64_t G = H->ngroups;
-  if (!cur_rows) return fail(ORCG_INVALID_ARGUMENT, "row groups without row starts");
-  const uint8_t* mask = slot == kSlotPresent ? cur_in_nn : cur_row_nn;
-  const int64_t* prefix = cur_rows;
+  if (!r.rg_rows) return fail(ORCG_INVALID_ARGUMENT, "row groups without row starts");
+  const uint8_t* mask = slot == kSlotPresent ? r.in_nn : r.row_nn;
   int rc;
   if (mask) {
     // the row groups' set-row prefix and the segment table in one launch
     ORCG_ALLOC(int64_t, pre, G + 1);
     ORCG_ALLOC(uint64_t, seg, 2 * G);
-    if ((rc = launch_rg_prefix_segtab(act.ctx, mask, cur_n, cur_rows, G, (const int64_t*)(D->d_stage + sb.rg_off), boolean,
-                                      pre, seg)))
+    if ((rc = launch_rg_prefix_segtab(act.ctx, mask, r.n, r.rg_rows, G, (const int64_t*)(D->d_stage + sb.rg_off),
+                                      boolean, pre, seg)))
       return fail_ctx(rc);
     *d_seg = seg;
     *nseg = G;
     return ORCG_OK;
   }
   ORCG_ALLOC(uint64_t, seg, 2 * G);
-  if ((rc = launch_rg_segtab(act.ctx, (const int64_t*)(D->d_stage + sb.rg_off), prefix, G, boolean, seg)))
+  if ((rc = launch_rg_segtab(act.ctx, (const int64_t*)(D->d_stage + sb.rg_off), r.rg_rows, G, boolean, seg)))
     return fail_ctx(rc);
   *d_seg = seg;
   *nseg = G;
@@ -76,7 +75,8 @@ bool orcg_reader::device_work(uint32_t id) const {
   return true;
 }
 
-int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t** pout, const uint64_t* dcount) {
+int orcg_reader::int_stream(Col& c, const StreamDesc& d, const Rows& r, uint64_t count, int64_t** pout,
+                            const uint64_t* dcount) {
   const int slot = d.slot;
   const StripeBatch::Values* done = B.find((uint32_t)(&c - H->cols.data()), slot);
   if (done && done->count == count) {
@@ -98,7 +98,7 @@ int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t
   const uint8_t* d_src = D->d_stage + sb.host_off;
   const uint64_t* d_seg;
   uint64_t nseg;
-  int rc = segments(c, slot, false, &d_seg, &nseg);
+  int rc = segments(c, slot, false, r, &d_seg, &nseg);
   if (rc) return rc;
   const int sg = d.is_signed ? 1 : 0;
   madd(kMDecodeCall, 1);
@@ -119,7 +119,7 @@ int orcg_reader::int_stream(Col& c, const StreamDesc& d, uint64_t count, int64_t
   return rc ? fail_ctx(rc) : ORCG_OK;
 }
 
-int orcg_reader::byte_stream(Col& c, const StreamDesc& d, uint64_t count, uint8_t* out, uint64_t* d_ones,
+int orcg_reader::byte_stream(Col& c, const StreamDesc& d, const Rows& r, uint64_t count, uint8_t* out, uint64_t* d_ones,
                              const uint64_t* d_count) {
   const int slot = d.slot;
   const bool boolean = d.coding == kBoolRle;
@@ -135,7 +135,7 @@ int orcg_reader::byte_stream(Col& c, const StreamDesc& d, uint64_t count, uint8_
   }
   const uint64_t* d_seg;
   uint64_t nseg;
-  int rc = segments(c, slot, boolean, &d_seg, &nseg);
+  int rc = segments(c, slot, boolean, r, &d_seg, &nseg);
   if (rc) return rc;
   madd(kMByteCall, 1);
   rc = timed(1, [&]() -> int {

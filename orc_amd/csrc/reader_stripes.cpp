@@ -133,7 +133,7 @@ int orcg_reader::first_error(int inline_rc) {
 // batched launches, every selected column's launches, the read-back copy and
 // the flight's event. Host checks wait for finish().
 void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
-  F = &fl;
+  const Bound bound(this, fl, &hs, &ds);
   fl.hs = &hs;
   fl.ds = &ds;
   fl.t0 = now_s();
@@ -153,8 +153,6 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
     fl.err_col = err_col;
     fl.err_msg = last_error;
     fl.t1 = now_s();
-    H = nullptr;
-    D = nullptr;
   };
   ds.stripe = hs.stripe;
   ds.pool.release_all();
@@ -218,16 +216,9 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
   }
   fl.defer_used = 0;
   fl.checks.clear();
-  H = &hs;
-  D = &ds;
   // the context's own record for this stripe rides the read-back block (the
   // stripe's one copy back replaces sync_ctx's synchronous record read)
-  struct OwnRecord {
-    Ctx* c;
-    unsigned long long* saved;
-    ~OwnRecord() { c->d_err = saved; }
-  } own_rec{act.ctx, act.ctx->d_err};
-  act.ctx->d_err = (unsigned long long*)(ds.d_rb + 2 * nc);
+  const ErrRecordScope own_rec(act.ctx, (unsigned long long*)(ds.d_rb + 2 * nc));
   B.reset();
   const uint64_t nrows = nrows_stripe;
   const int64_t* rg_rows = hs.ngroups ? (const int64_t*)(ds.d_stage + hs.rows_off) : nullptr;
@@ -277,8 +268,9 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
       (B.ev_pre || hipEventCreateWithFlags(&B.ev_pre, hipEventDisableTiming) == hipSuccess))
     pre_lane = ctx_lane(act.ctx, 0);
   if (!rc && pre_lane) {
-    rc = hip_check(act.ctx, hipEventRecord(act.ctx->ev_fork, act.ctx->stream), "fork event");
-    if (!rc) rc = hip_check(act.ctx, hipStreamWaitEvent(pre_lane->stream, act.ctx->ev_fork, 0), "fork wait");
+    // (never joined: the gathers and the stripe's end wait for ev_pre instead)
+    LaneFork lf(act.ctx);
+    if (!(rc = lf.begin())) rc = lf.lane(0, &pre_lane);
     if (!rc && (rc = run_multi(pre_lane, B.launches))) act.ctx->last_error = pre_lane->last_error;
     if (!rc) rc = hip_check(act.ctx, hipEventRecord(B.ev_pre, pre_lane->stream), "dictionary batch event");
     if (rc) rc = fail_ctx(rc);
@@ -309,32 +301,22 @@ void orcg_reader::issue(HostStage& hs, DevSlot& ds, Flight& fl) {
     (void)hipEventRecord(fl.done, act.ctx->stream);
   }
   fl.enqueued = true;
-  H = nullptr;
-  D = nullptr;
 }
 
 // Device half, host side: the first error in column order, as the reference
 // raises them one column at a time, then the stripe's column views.
 int orcg_reader::finish(Flight& fl) {
-  F = &fl;
-  H = fl.hs;
-  D = fl.ds;
+  const Bound bound(this, fl, fl.hs, fl.ds);
   HostStage& hs = *fl.hs;
   DevSlot& ds = *fl.ds;
   int rc = fl.rc;
-  if (!fl.enqueued) {  // failed before anything was enqueued
-    H = nullptr;
-    D = nullptr;
-    return fail(rc, fl.err_msg);
-  }
+  if (!fl.enqueued) return fail(rc, fl.err_msg);  // failed before anything was enqueued
   err_col = fl.err_col;
   last_error = fl.err_msg;
   rc = first_error(rc);
   fl.checks.clear();
   ds.out.clear();
   for (const Col& c : hs.cols) ds.out.emplace_back(c, !rc);
-  H = nullptr;
-  D = nullptr;
   const double t_end = now_s();
   // the upload's and the decode's GPU time (the flight's events, complete
   // here: first_error waited for `done`); host clocks without them

@@ -25,6 +25,17 @@ at the child's value count at the parent row group's first row.
   N8  struct<s:string>, direct, 8,193 rows (three 4,096-value scan tiles);
       bad: the last length negative, the last two 2^63 - 1 (the running
       total wraps at the last), the blob one byte short.
+  N9  struct<a:array<bigint>, s:string, m:map<string,bigint>,
+      u:uniontype<bigint,boolean>, x:bigint, t:string, b:array<tinyint>>,
+      stride 64, 2,101 rows, no PRESENT on the root: seven top-level subtrees
+      (the struct's fork over the side lanes, two subtrees to a lane), three
+      lists / maps waiting for the fork's next level (the map's 64-entry
+      dictionary keys and its values on two lanes), nulls in a, its elements,
+      s, m, its values, u, its children and x; t (direct) and b have none (a
+      batched length scan and batched LENGTH streams beside the keys'
+      pre-loaded dictionary). Column ids 0..13: the keys are 5, u is 7, t 11.
+      Bad: the key index = the dictionary's size at keys 5 and 1,500; tag 3
+      at the union's non-null rows 7 and 1,000; t's blob one byte short.
   Bad N3: tag 3 at non-null rows 1,234 and 4,000, tag 255 at the last.
   Bad N2 (16 and 4097 entries): entry index = the dictionary's size at key
   2,047 (the last of the first 2,048-row tile) and at key 3,000.
@@ -413,8 +424,59 @@ def n8(bad=None):
     return NestedFile(tree, rows, 1000, 80, tweak=tweak)
 
 
+# ---- N9 -----------------------------------------------------------------------------
+N9_ROWS, N9_STRIDE, N9_DICT, N9_BAD_KEYS, N9_BAD_TAGS = 2101, 64, 64, (5, 1500), (7, 1000)
+N9_KEYS, N9_UNION, N9_T = 5, 7, 11  # column ids
+
+
+@functools.lru_cache(maxsize=None)
+def n9(bad=()):
+    """bad: any of "index" (the keys), "tag" (the union), "short" (t's blob)."""
+    rng = np.random.default_rng(9)
+    n, D = N9_ROWS, N9_DICT
+
+    def maybe(p, v):
+        return None if rng.random() < p else v
+
+    keys = iter(np.concatenate([rng.permutation(D), rng.integers(0, D, size=5 * n)]).tolist())
+    rows = []
+    for i in range(n):
+        tag = int(rng.integers(0, 2))
+        rows.append({
+            "a": maybe(0.15, [maybe(0.2, int(v)) for v in rng.integers(-(1 << 40), 1 << 40, size=rng.integers(0, 5))]),
+            "s": maybe(0.1, "s%d" % i * int(rng.integers(0, 3))),
+            "m": maybe(0.15, [("k%02d" % next(keys), maybe(0.2, int(rng.integers(-1000, 1000))))
+                              for _ in range(int(rng.integers(0, 5)))]),
+            "u": maybe(0.1, (tag, maybe(0.15, bool(rng.integers(0, 2)) if tag else int(rng.integers(-(1 << 50), 1 << 50))))),
+            "x": maybe(0.2, int(rng.integers(-(1 << 30), 1 << 30))),
+            "t": "t%d" % i * int(rng.integers(0, 3)),
+            "b": [int(v) for v in rng.integers(-128, 128, size=rng.integers(0, 4))],
+        })
+    tree = Node("struct", [Node("list", [Node("long", nullable=True)], nullable=True), Node("string", nullable=True),
+                           Node("map", [Node("string", dictionary=True), Node("long", nullable=True)], nullable=True),
+                           Node("union", [Node("long", nullable=True), Node("boolean", nullable=True)], nullable=True),
+                           Node("long", nullable=True), Node("string"), Node("list", [Node("byte")])],
+                ["a", "s", "m", "u", "x", "t", "b"])
+
+    def tweak(cols):
+        assert [c.node.kind for c in cols] == ["struct", "list", "long", "string", "map", "string", "long", "union",
+                                               "long", "boolean", "long", "string", "list", "byte"]
+        assert len(cols[N9_KEYS].entries) == D and cols[N9_KEYS].n > N9_BAD_KEYS[1]
+        assert cols[N9_UNION].tags.size > N9_BAD_TAGS[1]
+        if "index" in bad:
+            for k in N9_BAD_KEYS:
+                cols[N9_KEYS].dense[k] = D
+        if "tag" in bad:
+            for k in N9_BAD_TAGS:
+                cols[N9_UNION].tags[k] = 3
+        if "short" in bad:
+            cols[N9_T].blob_cut = 1
+
+    return NestedFile(tree, rows, N9_STRIDE, 9, tweak=tweak)
+
+
 GOOD = {"N1": n1, "N2-16": lambda: n2(16), "N2-4096": lambda: n2(4096), "N2-4097": lambda: n2(4097), "N3": n3,
-        "N4": n4, "N5": n5, "N6": n6, "N7-65536": lambda: n7(65536), "N7-65537": lambda: n7(65537), "N8": n8}
+        "N4": n4, "N5": n5, "N6": n6, "N7-65536": lambda: n7(65536), "N7-65537": lambda: n7(65537), "N8": n8, "N9": n9}
 
 UNION_TAG = "Invalid union tag 3 for union with 3 children"
 DICT_INDEX = "Entry index out of range in StringDictionaryColumn"
@@ -422,6 +484,7 @@ DICT_NEGATIVE = "Negative dictionary entry length for column 1"
 STR_NEGATIVE = "Negative string length in StringDirectColumnReader for column 1"
 STR_OVERFLOW = "String length overflow in StringDirectColumnReader for column 1"
 STR_SHORT = "failed to read in StringDirectColumnReader.next"
+UNION_TAG_2 = "Invalid union tag 3 for union with 2 children"
 BAD = {"N3-tags": (lambda: n3(bad=True), UNION_TAG),
        "N2-16-index": (lambda: n2(16, bad=True), DICT_INDEX),
        "N2-4097-index": (lambda: n2(4097, bad=True), DICT_INDEX),
@@ -429,4 +492,10 @@ BAD = {"N3-tags": (lambda: n3(bad=True), UNION_TAG),
        "N7-65537-negative": (lambda: n7(65537, bad=True), DICT_NEGATIVE),
        "N8-negative": (lambda: n8("negative"), STR_NEGATIVE),
        "N8-wrap": (lambda: n8("wrap"), STR_OVERFLOW),
-       "N8-short": (lambda: n8("short"), STR_SHORT)}
+       "N8-short": (lambda: n8("short"), STR_SHORT),
+       # the earliest column's error, across the fork's lanes and levels: the keys (column 5, a device record of
+       # fork level 1) before t's blob (column 11, a deferred check of level 0) and before the union's tags (column
+       # 7, an inline failure of level 0: StructColumnReader::next reads m before u); the tags before t's blob
+       "N9-index": (lambda: n9(("index", "short")), DICT_INDEX),
+       "N9-tag": (lambda: n9(("index", "tag")), DICT_INDEX),
+       "N9-tag-short": (lambda: n9(("tag", "short")), UNION_TAG_2)}

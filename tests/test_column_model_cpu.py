@@ -8,13 +8,18 @@ and every crafted file of tests/nested_files.py against pyarrow's ORC reader
 Who vouches for which crafted file:
   N1, N2 (16 / 4096 / 4097 entries), N5, N6, N7 (65,536 / 65,537), N8:
       pyarrow reads every row equal to the rows the file was built from.
+  N9: the same (its union's values compared without their tags).
   N3, N4: pyarrow (unions come as sparse_union: the values equal the rows',
       the type codes equal flatten()'s tags on the non-null rows).
   Every file with a row index: the oracle's RleDecoderV2 / ByteRleDecoder,
       sought to every row group's positions, decode the values flatten() has
       there (pyarrow's whole-file read never seeks).
-  Bad N2 (16 / 4097), bad N7 (both), N8 one byte short: pyarrow raises the
-      reference's error.
+  Bad N2 (16 / 4097), bad N7 (both), N8 one byte short, N9-index (bad keys
+      and t one byte short: the keys' error, column 5 before column 11):
+      pyarrow raises the reference's error.
+  N9-tag, N9-tag-short: bad union tags, which pyarrow cannot take (below): the
+      oracle reads the crafted tags back; the order of the three errors is
+      StructColumnReader::next's, field by field (m, then u, then t).
   Bad N3, N8 negative, N8 wrap: pyarrow 25's bundled ORC reader predates the
       reference's checks (getCheckedUnionTag, computeSize's addLength) and
       crashes the process on them, so it is not run on these: the oracle's
@@ -247,7 +252,7 @@ def test_oracle_decoders_sought_to_every_row_group(name):
     assert sought > 0
 
 
-PYARROW_RAISES = ["N2-16-index", "N2-4097-index", "N7-65536-negative", "N7-65537-negative", "N8-short"]
+PYARROW_RAISES = ["N2-16-index", "N2-4097-index", "N7-65536-negative", "N7-65537-negative", "N8-short", "N9-index"]
 
 
 @pytest.mark.parametrize("name", PYARROW_RAISES)
@@ -269,6 +274,18 @@ def test_bad_files_the_bundled_reader_cannot_take():
     a, b = nf.N3_BAD
     assert np.flatnonzero(tags >= 3).tolist() == [a, b, tags.size - 1]
     assert cm.union(tags, 3)[2] == (a << 8) | 3 and nf.UNION_TAG == "Invalid union tag 3 for union with 3 children"
+    # bad N9's tags (N9-tag, N9-tag-short); in N9-tag the keys' bad indices, which pyarrow raises for
+    # N9-index, belong to column 5, read before the union (column 7)
+    for name in ("N9-tag", "N9-tag-short"):
+        f = nf.BAD[name][0]()
+        u = f.cols[nf.N9_UNION]
+        tags = oracle.ByteRleDecoder(f.crafted[nf.N9_UNION].streams[1][1]).next(u.tags.size)
+        np.testing.assert_array_equal(tags, u.tags)
+        assert np.flatnonzero(tags >= 2).tolist() == list(nf.N9_BAD_TAGS)
+        assert cm.union(tags, 2)[2] == (nf.N9_BAD_TAGS[0] << 8) | 3
+        assert nf.BAD["N9-tag-short"][1] == "Invalid union tag 3 for union with 2 children"
+    keys = nf.BAD["N9-tag"][0]().cols[nf.N9_KEYS]
+    assert np.flatnonzero(keys.dense >= len(keys.entries)).tolist() == list(nf.N9_BAD_KEYS) and nf.N9_KEYS < nf.N9_UNION
     last_tile = 2 * 4096
     for bad, flags in (("negative", (1, None)), ("wrap", (0, 1))):
         f = nf.n8(bad)

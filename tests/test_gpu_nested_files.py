@@ -4,13 +4,18 @@ PRESENT streams below the root, under a row index of many small row groups
 (the look-back over row groups, the child row-group starts, the parent-mask ->
 child-count chain), dictionaries on either side of the batched launch's 4,096
 entries and of the one-workgroup scan's 65,536, and direct strings past the
-one-workgroup scan. Every column is compared array by array with
+one-workgroup scan, and (N9) a struct of seven fields forked over the side
+lanes. Every column is compared array by array with
 column_model.flatten()'s ground truth (null rows are unspecified: compared on
 the rows that are not null); tests/test_column_model_cpu.py proves on the CPU
 that pyarrow and the oracle read the same bytes to the same values. The bad
 files raise the reference's errors. Every comparison is exact.
 
 Needs a real MI355X: run with `pytest -m gpu`."""
+import os
+import subprocess
+import sys
+
 import numpy as np
 import pytest
 
@@ -93,9 +98,9 @@ def test_stripe_columns_equal_the_ground_truth(ctx, name):
     check_columns(f, b, name)
     if name == "N6":
         assert stats["row_index"] == 0 and stats["host_plan"] > 0
-    elif name[:2] in ("N1", "N2", "N3", "N4", "N5"):
+    elif name[:2] in ("N1", "N2", "N3", "N4", "N5", "N9"):
         assert stats["row_index"] > 0, stats
-    if name in ("N5", "N2-16", "N2-4096"):
+    if name in ("N5", "N2-16", "N2-4096", "N9"):
         assert stats["batched"] > 0, stats
 
 
@@ -185,3 +190,46 @@ def test_bad_files_raise_the_reference_errors(ctx, name):
     assert text in str(e.value), name
     good = nf.n8()
     check_columns(good, read(good, ctx)[1], "N8 after " + name)
+
+
+N9_BAD = ["N9-index", "N9-tag", "N9-tag-short"]
+
+
+def lanes_child():
+    """What a child process of the test below runs: N9 and its three bad
+    files through the checks of the tests above, on a context of its own."""
+    ctx = orc_amd.Context(0)
+    good = nf.GOOD["N9"]()
+    for batching in (True, False):
+        check_columns(good, read(good, ctx, batching=batching)[1], "N9 batching %s" % batching)
+    for name in N9_BAD:
+        make, text = nf.BAD[name]
+        f = make()
+        for batching in (True, False):
+            r = orc_amd.Reader(f.data, ctx)
+            r.set_stream_batching(batching)
+            with pytest.raises(orc_amd.ParseError) as e:
+                r.read_stripe(0)
+            assert text in str(e.value), (name, batching, str(e.value))
+    check_columns(good, read(good, ctx)[1], "N9 after the bad files")
+
+
+def test_one_and_two_side_lanes_read_n9_alike():
+    """ORCG_LANES is read once per process: a fresh child python with one
+    lane (no fork at all), then one with two (seven subtrees on two lanes, a
+    map's values on the other lane of its keys), one after the other; each
+    reads N9 and raises the bad files' errors as the default four lanes do.
+    A first child that does not end by itself (a signal, the time limit)
+    keeps the second from starting."""
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = "import sys; sys.path[:0] = [%r, %r]; import test_gpu_nested_files as t; t.lanes_child()" % (
+        here, os.path.dirname(here))
+    for lanes in ("1", "2"):
+        env = dict(os.environ, ORCG_LANES=lanes)
+        out = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", code], capture_output=True, text=True,
+                             env=env)
+        assert out.returncode in (0, 1), "ORCG_LANES=%s: exit status %d\n%s" % (lanes, out.returncode, out.stderr[-3000:])
+        if lanes == "1":
+            first = out
+    for lanes, out in (("1", first), ("2", out)):
+        assert out.returncode == 0, "ORCG_LANES=%s\n%s" % (lanes, out.stderr[-3000:])
