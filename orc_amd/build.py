@@ -16,15 +16,12 @@ OUT = os.path.join(HERE, "liborcgpu_prof.so" if PROF else ("liborcgpu_ab.so" if 
 OBJ = os.path.join(HERE, "build_prof" if PROF else ("build_ab" if AB else "build"))
 ARCH = os.environ.get("ORCG_OFFLOAD_ARCH", "gfx950")
 
-SOURCES = ["rlev2_kernels.hip", "rlev2_tiled.hip", "rlev2_expand.hip", "byterle_kernels.hip", "column_kernels.hip", "rlev1_kernels.hip", "decimal_kernels.hip", "convert_kernels.hip", "arrow_kernels.hip", "inflate_kernels.hip", "filter_kernels.hip", "orcg_ctx.cpp", "pinned.cpp", "host_plan.cpp", "rlev2_route.cpp", "inflate_plan.cpp", "inflate_api.cpp", "filter_plan.cpp", "filter_api.cpp", "host_decode.cpp", "rlev2_api.cpp", "debug_api.cpp",
+SOURCES = ["rlev2_kernels.hip", "rlev2_tiled_inst_serial.hip", "rlev2_tiled_inst_dense.hip", "rlev2_tiled_inst_union.hip", "rlev2_tiled.cpp", "rlev2_expand.hip", "byterle_kernels.hip", "column_kernels.hip", "rlev1_kernels.hip", "decimal_kernels.hip", "convert_kernels.hip", "arrow_kernels.hip", "inflate_kernels.hip", "filter_kernels.hip", "orcg_ctx.cpp", "pinned.cpp", "host_plan.cpp", "rlev2_route.cpp", "inflate_plan.cpp", "inflate_api.cpp", "filter_plan.cpp", "filter_api.cpp", "host_decode.cpp", "rlev2_api.cpp", "debug_api.cpp",
            "multi_launch.cpp", "rlev1_api.cpp", "orc_file.cpp", "reader_api.cpp", "reader_prepare.cpp",
            "reader_collect.cpp", "reader_streams.cpp", "reader_decode.cpp", "reader_fork.cpp", "reader_stripes.cpp",
            "row_reader.cpp", "byterle_api.cpp", "decimal_api.cpp", "convert_api.cpp", "arrow_api.cpp", "arrow_export.cpp", "timezone.cpp", "encoder.cpp", "java_face.cpp"]
 if PROF or AB:
     SOURCES.append("probe_kernels.hip")
-HEADERS = ["orcg_internal.hh", "dev_error.hh", "host_plan.hh", "rlev2_route.hh", "inflate_plan.hh", "host_decode.hh", "device_util.hh", "rlev2_device.hh", "orc_file.hh", "timezone.hh", "reader_layout.hh", "reader_internal.hh", "read_type.hh", "arrow_internal.hh", "filter_plan.hh", "filter_internal.hh", os.path.join("..", "..", "include", "orcg.h"),
-           os.path.join("..", "..", "include", "orcg_reader.h"), os.path.join("..", "..", "include", "orcg_arrow.h"),
-           os.path.join("..", "..", "include", "orcg_filter.h")]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-result", "-Wno-unused-value"]
@@ -39,24 +36,37 @@ def _mtime(p):
     return os.path.getmtime(p) if os.path.exists(p) else 0.0
 
 
+def stale(obj, src, dep, tools=(os.path.abspath(__file__),)):
+    """Whether `obj` has to be compiled again: it is missing, it has no
+    dependency file `dep` (the compiler's -MD output, make syntax) yet, or its
+    source, a file that `dep` names or one of `tools` is missing or not older
+    than it."""
+    if not os.path.exists(obj) or not os.path.exists(dep):
+        return True
+    with open(dep) as f:
+        words = f.read().replace("\\\n", " ").split()
+    deps = [w for w in words if not w.endswith(":")]  # (the rule's target ends in a colon)
+    built = os.path.getmtime(obj)
+    return any(not os.path.exists(p) or os.path.getmtime(p) >= built for p in [src, *tools, *deps])
+
+
 def build(force=False, verbose=False):
     os.makedirs(OBJ, exist_ok=True)
-    hdr_time = max(_mtime(os.path.join(CSRC, h)) for h in HEADERS)
     objs, cmds = [], []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
         obj = os.path.join(OBJ, s + ".o")
         objs.append(obj)
-        if not force and _mtime(obj) > max(_mtime(src), hdr_time):
+        if not force and not stale(obj, src, obj + ".d"):
             continue
-        cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + FLAGS + ["-MD", "-MF", obj + ".d", "-c", src, "-o", obj]
         if s.endswith(".hip"):
             cmd[1:1] = ["-x", "hip", "--offload-arch=" + ARCH]
         else:
             cmd[1:1] = ["-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
         cmds.append(cmd)
-    # translation units compile in parallel (the slowest, rlev2_tiled.hip, first)
-    cmds.sort(key=lambda c: "rlev2_tiled" not in c[-3])
+    # translation units compile in parallel (the slowest, the rlev2_tiled instance units, first)
+    cmds.sort(key=lambda c: "rlev2_tiled_inst_" not in c[-3])
     from concurrent.futures import ThreadPoolExecutor
 
     def run(cmd):

@@ -34,7 +34,7 @@ using GroupParser = uint32_t (*)(const uint8_t* s, uint64_t len, uint64_t pos, u
 // stream cuts or a corrupt header fails before any of its values. A DELTA
 // run's two varints end inside the run's first kRlev2HdrLim bytes (every
 // writer's take <= 22), or the run is a bad read: the device kernels' limit
-// (rlev2_tiled.hip kHdrLim, parse_run's `lim`), kept here so that a plan and
+// (rlev2_tiled_common.hh kHdrLim, parse_run's `lim`), kept here so that a plan and
 // the kernels agree on every stream.
 constexpr uint32_t kRlev2HdrLim = 64;
 uint32_t host_parse_run(const uint8_t* s, uint64_t len, uint64_t pos, uint64_t* run_len, uint64_t* run_end,

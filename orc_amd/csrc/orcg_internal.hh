@@ -50,7 +50,7 @@ struct Ctx {
   void* d_scratch[kScratchSlots] = {};
   size_t scratch_cap[kScratchSlots] = {};
   int rlev2_variant = ORCG_RLEV2_TILED;  // which RLEv2 kernel to launch
-  void* d_defer = nullptr;  // RLEv2 short-run segment queue (rlev2_tiled.hip defer_queue)
+  void* d_defer = nullptr;  // RLEv2 short-run segment queue (rlev2_tiled.cpp defer_queue)
   uint64_t defer_cap = 0;
   uint64_t defer_seq = 0;  // serial + drain launch pairs so far (their entries' stamps)
   int num_cus = 0;         // compute units of `device` (0 = not queried yet)
@@ -219,7 +219,7 @@ struct RunTab {
 int launch_rlev2_expand(Ctx* ctx, const Rlev2Args& a, const RleJob* jobs_d, uint32_t njobs, const RunTab& rt);
 void warm_rlev2_expand(hipStream_t s);
 
-// A tiled instance (rlev2_tiled.hip): the pinned one, or the one the default
+// A tiled instance (rlev2_tiled.cpp): the pinned one, or the one the default
 // routes the stream to (rlev2_route.hh, which also lists the variants).
 int launch_rlev2_tiled(Ctx* ctx, const Rlev2Args& a);
 
@@ -269,7 +269,7 @@ inline bool joins_first(MultiLaunch::Kind k) {
 }
 int plan_rlev2_multi(Ctx* ctx, const RleJob* jobs, uint32_t njobs, std::vector<MultiLaunch>& out);
 // One planned RLEv2 launch (kRlev2) over its staged job table, on ctx's stream:
-// run_multi's entry into the tiled instances (rlev2_tiled.hip).
+// run_multi's entry into the tiled instances (rlev2_tiled.cpp).
 int launch_rlev2_tiled_jobs(Ctx* ctx, const MultiLaunch& m);
 // A varint DATA stream's tile counts and their scan (the first value of each
 // kVarintTile-byte tile) ahead of its decode: the decimal columns' first two

@@ -1,7 +1,7 @@
 // RLEv2 launch routing: which tiled instance a stream or a group of streams
 // gets, whether the union instance runs in one pass or two, and how the jobs
 // of a multi-stream launch are grouped and ordered. Host arithmetic only:
-// nothing here needs HIP (the launcher, rlev2_tiled.hip, supplies the CU
+// nothing here needs HIP (the launcher, rlev2_tiled.cpp, supplies the CU
 // count), and tests/cxx/rlev2_route_test.cpp pins every rule and edge under
 // the host sanitizers.
 #pragma once
@@ -15,7 +15,7 @@ namespace orcg {
 // The instances by their public numbers (ctx->rlev2_variant, include/orcg.h):
 // 0 = the density-adaptive default, 1 = the wave-walk kernel
 // (rlev2_kernels.hip), kRlev2FirstTiled .. kMaxRlev2Variant pin one tiled
-// instance (rlev2_tiled.hip kInstances holds their parameters; the parity
+// instance (rlev2_tiled.cpp kInstances holds their parameters; the parity
 // tests run each).
 constexpr int kRlev2Default = 0;
 constexpr int kRlev2WaveWalk = 1;

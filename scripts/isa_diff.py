@@ -2,7 +2,17 @@
 """Compare the device assembly of one translation unit between two states of
 the tree: the check for a refactor that must not change the compiled kernels.
 
-    scripts/isa_diff.py rlev2_tiled.hip REV_A [REV_B] [-D MACRO[=V]]... [--by-order]
+    scripts/isa_diff.py rlev2_expand.hip REV_A [REV_B] [-D MACRO[=V]]... [--by-order]
+    scripts/isa_diff.py A.hip,B.hip REV_A [REV_B] [--units-b C.hip,D.hip,E.hip]
+
+A side may be several units, and the two sides different ones (a unit that
+was split): the pieces of a side's units are pooled by name. A piece that
+several units hold in the same words (a per-unit warm kernel, a per-unit
+table) counts once and is listed; one that differs between a side's units
+keeps its unit's name and is listed as on one side only. With several units
+the .amdgpu_metadata block is cut into one piece per kernel entry, and the
+unit's register maximums, which follow its last function whichever that is,
+into one of their own.
 
 REV_B defaults to the working tree. For each side, orc_amd/csrc and include/
 are materialised in a temporary directory and the unit is compiled with
@@ -50,17 +60,23 @@ def materialise(rev, dst):
     subprocess.run(["tar", "-x", "-C", dst], input=tar, check=True)
 
 
-def compile_asm(rev, tu, defines, workdir):
+def compile_asm(rev, tus, defines, workdir):
+    """The assembly of each unit of `tus` at `rev`, compiled side by side."""
     hipcc, arch, flags = build_settings()
     materialise(rev, workdir)
-    out = os.path.join(workdir, "out.s")
-    cmd = [hipcc, "-x", "hip", "--offload-arch=" + arch] + flags + ["-D" + d for d in defines]
-    cmd += ["--cuda-device-only", "-S", os.path.join(workdir, "orc_amd", "csrc", tu), "-o", out]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    if r.returncode != 0:
-        sys.exit("%s: compile failed\n%s" % (rev or "working tree", r.stdout))
-    with open(out) as f:
-        return f.read()
+
+    def one(tu):
+        out = os.path.join(workdir, tu + ".s")
+        cmd = [hipcc, "-x", "hip", "--offload-arch=" + arch] + flags + ["-D" + d for d in defines]
+        cmd += ["--cuda-device-only", "-S", os.path.join(workdir, "orc_amd", "csrc", tu), "-o", out]
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        if r.returncode != 0:
+            sys.exit("%s %s: compile failed\n%s" % (rev or "working tree", tu, r.stdout))
+        with open(out) as f:
+            return f.read()
+
+    with ThreadPoolExecutor(len(tus)) as ex:
+        return list(ex.map(one, tus))
 
 
 FUNC = re.compile(r"^\s*\.type\s+(\S+),@(?:function|object)")
@@ -103,25 +119,87 @@ def pieces(text, by_order):
     return out
 
 
+def split_metadata(ps):
+    """The "(metadata)" piece cut into one piece per kernel entry, named by the
+    entry's .name; what stands around the entries stays "(metadata)". The
+    unit's register maximums, which follow its last function whichever that
+    is, become a piece too."""
+    out = []
+    for name, lines in ps:
+        if name != "(metadata)":
+            cut = next((i for i, ln in enumerate(lines) if ".AMDGPU.gpr_maximums" in ln), len(lines))
+            out.append((name, lines[:cut]))
+            if cut < len(lines):
+                out.append(("(gpr maximums)", lines[cut:]))
+            continue
+        rest, entry = [], None
+        for ln in lines + [""]:
+            if entry is not None and not ln.startswith("    "):  # the entry's fields are indented under it
+                kernel = next(x.split(":", 1)[1].strip() for x in entry if x.startswith("    .name:"))
+                out.append(("(metadata) " + kernel, entry))
+                entry = None
+            if ln.startswith("  - ."):
+                entry = []
+            (rest if entry is None else entry).append(ln)
+        out.append((name, rest[:-1]))
+    return out
+
+
+def pool(per_unit, units):
+    """One list of pieces for a side compiled from several units: a piece that
+    every unit holds in the same words (the preamble, a per-unit data object)
+    counts once, and is listed when more than one unit holds it; a name whose
+    pieces differ between the units stays as it is and cannot pair."""
+    out, seen = [], {}
+    for unit, ps in zip(units, per_unit):
+        for name, lines in ps:
+            if name not in seen:
+                seen[name] = (len(out), [unit])
+                out.append((name, lines))
+            elif out[seen[name][0]][1] == lines:
+                seen[name][1].append(unit)
+            else:
+                out.append(("%s [%s]" % (name, unit), lines))
+    for name, (_, us) in seen.items():
+        if len(us) > 1 and not name.startswith("("):
+            print("%s: once in each of %s, the same words" % (name, ", ".join(us)))
+    return out
+
+
+def compare_sides(ta, ua, tb, ub, by_order):
+    """The two sides' pieces: a side's units pooled by name. With more than one
+    unit on a side the metadata goes kernel by kernel on both."""
+    sides = []
+    for texts, units in ((ta, ua), (tb, ub)):
+        per_unit = [pieces(t, by_order) for t in texts]
+        if len(ua) > 1 or len(ub) > 1:
+            per_unit = [split_metadata(ps) for ps in per_unit]
+        sides.append(per_unit[0] if len(units) == 1 else pool(per_unit, units))
+    return sides
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("tu", help="translation unit under orc_amd/csrc, e.g. rlev2_tiled.hip")
+    ap.add_argument("tu", help="translation unit(s) under orc_amd/csrc, e.g. rlev2_tiled.hip or a,b,c")
     ap.add_argument("rev_a")
     ap.add_argument("rev_b", nargs="?", default=None, help="default: the working tree")
+    ap.add_argument("--units-b", default=None, metavar="TU[,TU...]", help="REV_B's units (default: REV_A's)")
     ap.add_argument("-D", dest="defines", action="append", default=[], metavar="MACRO[=V]")
     ap.add_argument("--by-order", action="store_true", help="replace function symbols by their ordinals")
     ap.add_argument("--context", type=int, default=6, help="differing lines shown per function")
     args = ap.parse_args()
+    ua = args.tu.split(",")
+    ub = (args.units_b or args.tu).split(",")
 
     with tempfile.TemporaryDirectory(prefix="isa_diff_") as tmp:
         da, db = os.path.join(tmp, "a"), os.path.join(tmp, "b")
         os.makedirs(da)
         os.makedirs(db)
         with ThreadPoolExecutor(2) as ex:
-            fa = ex.submit(compile_asm, args.rev_a, args.tu, args.defines, da)
-            fb = ex.submit(compile_asm, args.rev_b, args.tu, args.defines, db)
+            fa = ex.submit(compile_asm, args.rev_a, ua, args.defines, da)
+            fb = ex.submit(compile_asm, args.rev_b, ub, args.defines, db)
             ta, tb = fa.result(), fb.result()
-    pa, pb = pieces(ta, args.by_order), pieces(tb, args.by_order)
+    pa, pb = compare_sides(ta, ua, tb, ub, args.by_order)
     bad = 0
     if not args.by_order:
         # pair the pieces by name (a change may reorder the functions, e.g.

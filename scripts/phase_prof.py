@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Where a tiled RLEv2 launch spends its time, per phase, from the kernel's
-own cycle counters (orc_amd/csrc/rlev2_tiled.hip PROF_MARK; build with
+own cycle counters (orc_amd/csrc/rlev2_tiled_common.hh PROF_MARK; build with
 ORCG_PHASE_PROF=1 python -m orc_amd.build, which writes liborcgpu_prof.so).
 Thread 0 of every workgroup adds the wall-clock ticks (100 MHz) between
 consecutive phase marks; the script prints each phase's share and its

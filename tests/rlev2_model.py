@@ -4,7 +4,7 @@ values, so it can say everything the format can), the decoder (RleDecoderV2
 readByte order, nextShortRepeats / nextDirect / nextPatched with
 adjustGapAndPatch / nextDelta, as orc_amd/csrc/rlev2_device.hh parse_run cites
 them), the kernels' geometry restated as data, the window schedule of the
-serial walk (rlev2_tiled.hip walk()), and the builders that put a run at a
+serial walk (rlev2_tiled_walk.hh walk()), and the builders that put a run at a
 named window byte. tests/test_rlev2_model_cpu.py proves the model against the
 oracle and that every shape holds what it claims; tests/
 test_gpu_rlev2_shapes.py compares every kernel instance with the model exactly.
@@ -30,14 +30,15 @@ SEGMENT_ERROR = "Stream position is not at a run boundary"
 # first value (include/orcg.h; the reference reads varints of any length)
 HDR_LIM = 64
 CONSTANTS = {
-    "rlev2_tiled.hip": dict(kThreads=256, kMaxRun=4608, kSlab=2048, kStage=256, kShortL=16, kVparL=256,
-                            ORCG_VPAR_MIN=16, kToDense=24, kToSerial=64, ORCG_TAB_TO_DENSE=128,
-                            ORCG_TAB_TO_SERIAL=512, ORCG_ITEM_MAX=64),
+    "rlev2_tiled_common.hh": dict(kThreads=256, kMaxRun=4608, kSlab=2048, kStage=256, kShortL=16, kVparL=256,
+                                  ORCG_VPAR_MIN=16, kToDense=24, kToSerial=64, ORCG_TAB_TO_DENSE=128,
+                                  ORCG_TAB_TO_SERIAL=512),
+    "rlev2_tiled_walk.hh": dict(ORCG_ITEM_MAX=64),
     "rlev2_expand.hip": dict(kRound=256),
     "rlev2_route.hh": dict(kSliceMax=1024, kMaxRlev2Variant=10),
     "host_plan.hh": dict(kRlev2HdrLim=HDR_LIM),
 }
-_T = CONSTANTS["rlev2_tiled.hip"]
+_T = dict(CONSTANTS["rlev2_tiled_common.hh"], **CONSTANTS["rlev2_tiled_walk.hh"])
 MAX_RUN, SLAB, SHORT_L, ITEM_MAX = _T["kMaxRun"], _T["kSlab"], _T["kShortL"], _T["ORCG_ITEM_MAX"]
 BLK = SLAB // _T["kThreads"]  # kBlk: bytes a thread owns in dense discovery
 SUPER = 8 * BLK               # kSup
@@ -48,7 +49,7 @@ LONGEST_RUN = 4356            # PATCHED W=64 L=512 bw=8, 31 entries of 64 bits
 _WINS = _T["kThreads"] // 64 * _T["kStage"] * 8 + SLAB // 8  # what a union instance's serial window adds
 
 # variant -> (kWin, what walks it, kWinS: the serial window of a union instance)
-# rlev2_tiled.hip kInstances' rows: kWin = KB * 1024, + 512 in dense-capable instances
+# rlev2_tiled.cpp kInstances' rows: kWin = KB * 1024, + 512 in dense-capable instances
 VARIANTS = {
     0: (None, "default", None),  # picks 2, 3, 6 or 8 by the stream's bytes per value
     1: (None, "wave-walk", None),

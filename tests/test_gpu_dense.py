@@ -1,6 +1,6 @@
 """GPU parity tests for the tiled kernel's dense (short-run) mode: parallel
 run discovery over slabs and lane-per-run expansion through the LDS stage
-(orc_amd/csrc/rlev2_tiled.hip). Streams are made of short
+(orc_amd/csrc/rlev2_tiled_dense.hh). Streams are made of short
 runs (SHORT_REPEAT-heavy low-cardinality columns, short DIRECT / DELTA runs)
 with long and PATCHED_BASE runs mixed in, so a window switches between the
 serial walk and dense mode. Bit-exact against the CPU oracle.
@@ -320,7 +320,7 @@ def test_short_wide_direct_default_routing_vs_oracle(signed):
 @pytest.mark.parametrize("bits", [7, 33, 64])
 @pytest.mark.parametrize("signed", [True, False])
 def test_value_parallel_expansion_vs_oracle(bits, signed):
-    """The dense expansion's value-parallel path (rlev2_tiled.hip dense_expand:
+    """The dense expansion's value-parallel path (rlev2_tiled_dense.hh dense_expand:
     SHORT_REPEAT / DIRECT / constant-step DELTA runs of 17-256 values inside
     dense segments, each value found by a binary search over the runs' first
     values): short-run segments (SHORT_REPEAT runs of 3-10 values) with DIRECT
@@ -430,7 +430,7 @@ def _skew_stream(rng, signed, n_target, long_kind, every):
 @pytest.mark.parametrize("long_kind", ["direct", "delta", "patched"])
 @pytest.mark.parametrize("signed", [True, False])
 def test_two_pass_skew_vs_oracle(long_kind, signed):
-    """The two-pass union decode (variant 6; rlev2_tiled.hip kOptTable +
+    """The two-pass union decode (variant 6; rlev2_tiled_kernel.hh kOptTable +
     rlev2_expand.hip) on row groups that mix 3-value SHORT_REPEAT runs with
     long DIRECT / variable-width DELTA / PATCHED_BASE runs: the long runs sit
     in tabled dense passes and straddle value slices (a DELTA run begun before

@@ -1,4 +1,4 @@
-"""GPU parity tests of the flat DIRECT path (rlev2_tiled.hip, kOptFlat): a
+"""GPU parity tests of the flat DIRECT path (rlev2_tiled_flat.hh, kOptFlat): a
 segment's leading chain of full 512-value DIRECT runs of one width >= 40 bits
 is validated by one header probe and expanded straight from memory, the rest
 of the segment goes through the windowed walk. Variant 2 (and the default for

@@ -1,4 +1,4 @@
-"""GPU parity tests of the flat DIRECT path's 16-byte form (rlev2_tiled.hip,
+"""GPU parity tests of the flat DIRECT path's 16-byte form (rlev2_tiled_flat.hh,
 kOptFlat16 / flat_expand16): full W=64 runs of a segment's leading chain are
 loaded as aligned 16-byte chunks, shifted in registers by the payload's offset
 mod 16 and stored two values per lane. Variant 2 (and the default for such

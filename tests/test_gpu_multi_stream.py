@@ -1,6 +1,6 @@
 """GPU parity tests of the multi-stream RLEv2 launches: a stripe's
 host-countable streams decoded by one launch per kernel instance over a job
-table (reader_collect.cpp collect -> queue_stream, rlev2_tiled.hip
+table (reader_collect.cpp collect -> queue_stream, rlev2_tiled.cpp
 plan_rlev2_multi -> run_multi; the kMulti instantiations of
 rlev2_tiled_kernel and rlev2_expand_kernel). There is no entry point to these
 instances but a file, so the streams of tests/multi_stream_files.py, built

@@ -422,7 +422,7 @@ def test_split_launches_every_variant(kind):
     instance, full range and value windows whose ends fall inside runs,
     against the generated values (the encoder's input, checked against the
     oracle below). With ORCG_SPLIT=k (k > 1) in the environment the launches
-    split each segment's values over k workgroups (rlev2_tiled.hip
+    split each segment's values over k workgroups (rlev2_tiled.cpp
     auto_split), each one walking the runs before its share: the same test
     covers that path."""
     import torch

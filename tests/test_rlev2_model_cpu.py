@@ -294,30 +294,38 @@ def check_constants(table):
 def test_the_models_constants_are_the_sources():
     check_constants(m.CONSTANTS)
     moved = {k: dict(v) for k, v in m.CONSTANTS.items()}
-    moved["rlev2_tiled.hip"]["kShortL"] += 1
+    moved["rlev2_tiled_common.hh"]["kShortL"] += 1
     with pytest.raises(AssertionError, match="kShortL is 16 in the source, 17 in the model"):
         check_constants(moved)  # the check can fail
-    text = open(os.path.join(ROOT, "orc_amd", "csrc", "rlev2_tiled.hip")).read()
+    csrc = os.path.join(ROOT, "orc_amd", "csrc")
+    common, walk, dense, kernel = (open(os.path.join(csrc, "rlev2_tiled_%s.hh" % f)).read()
+                                   for f in ("common", "walk", "dense", "kernel"))
     # what the model derives, or holds as a literal, as the source states it
-    assert "constexpr uint32_t kBlk = kSlab / kThreads;" in text and "constexpr uint32_t kDenseRuns = kSlab / 2;" in text
-    assert "constexpr uint32_t kSup = 8u * kBlk;" in text and "constexpr uint32_t kChunk = kWin - kMaxRun;" in text
-    assert "constexpr uint32_t kCap = kDense ? kDenseRuns : 512u;" in text and m.SERIAL_RUNS == 512
-    assert "constexpr uint32_t kWin = kWinKB * 1024u + (kDense ? 512u : 0u);" in text
-    assert "kUnion ? kWin + (uint32_t)(kWaves * kStage * 8 + kSlab / 8) : kWin;" in text
+    assert "constexpr uint32_t kBlk = kSlab / kThreads;" in common and "constexpr uint32_t kDenseRuns = kSlab / 2;" in common
+    assert "constexpr uint32_t kSup = 8u * kBlk;" in dense
+    assert "constexpr uint32_t kChunk = kWin - kMaxRun;" in kernel and "constexpr uint32_t kChunk = kWin - kMaxRun;" in walk
+    assert "constexpr uint32_t kCap = kDense ? kDenseRuns : 512u;" in kernel and m.SERIAL_RUNS == 512
+    assert "constexpr uint32_t kWin = kWinKB * 1024u + (kDense ? 512u : 0u);" in kernel
+    assert "kUnion ? kWin + (uint32_t)(kWaves * kStage * 8 + kSlab / 8) : kWin;" in kernel
     assert m.LONGEST_RUN == 4 + 8 + 512 * 8 + 31 * 8 <= m.MAX_RUN
     # the header limit has one definition (host_plan.hh, pinned above); the kernels name it
-    csrc = os.path.join(ROOT, "orc_amd", "csrc")
-    assert "constexpr uint32_t kHdrLim = kRlev2HdrLim;" in text
+    assert "constexpr uint32_t kHdrLim = kRlev2HdrLim;" in common
     assert "avail, kRlev2HdrLim, is_signed)" in open(os.path.join(csrc, "rlev2_expand.hip")).read()
     assert open(os.path.join(csrc, "rlev2_kernels.hip")).read().count("kRlev2HdrLim") >= 3
     assert not re.search(r"parse_run\([^;]*\b64u?,\s*is_signed", "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc))))
     # the instances, kInstances' rows: `{id, enqueue<options, window KB, min waves, kDense, kDefer>, drain}`,
     # the ids by their names in rlev2_route.hh
     ids = source_constants("rlev2_route.hh")
+    text = open(os.path.join(csrc, "rlev2_tiled.cpp")).read()
     table = text[text.index("constexpr Instance kInstances[] = {"):]
-    inst = re.findall(r"\{(kRlev2\w+), enqueue<[^,]+, (\d+), \d+, (\d+), \d+>, (?:nullptr|enqueue<[^>]*>)\}",
-                      table[:table.index("};")])
+    table = table[:table.index("};")]
+    inst = re.findall(r"\{(kRlev2\w+), enqueue<[^,]+, (\d+), \d+, (\d+), \d+>, (?:nullptr|enqueue<[^>]*>)\}", table)
     assert sorted(ids[v] for v, _, _ in inst) == list(range(2, 11))
+    # every enqueue<...> the table names is instantiated in exactly one instance unit, and nothing else is
+    units = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.startswith("rlev2_tiled_inst_"))
+    made = re.findall(r"^template void enqueue<([^>]*)>\(Ctx\*, const TiledLaunch&\);$", units, flags=re.M)
+    assert sorted(made) == sorted(set(re.findall(r"enqueue<([^>]*)>", table))) and len(made) >= 2
+    assert units.count("enqueue<") == len(made)
     for v, kb, dense in inst:
         v, kb = ids[v], int(kb)
         win, kind, wins = m.VARIANTS[v]
@@ -491,7 +499,7 @@ def test_dense_mix_and_slice_shapes():
     assert {(r.size, r.L) for r in seg(1)} == {(4, 512)} and len(seg(1)) * 4 > 2 * m.SLAB
     assert [max(r.L for r in seg(k)) for k in range(2, 6)] == [16, 17, 256, 257]
     sizes = sorted({r.size for k in range(6, len(s.segs)) for r in seg(k) if r.size > 14})
-    t = m.CONSTANTS["rlev2_tiled.hip"]
+    t = m.CONSTANTS["rlev2_tiled_common.hh"]
     for edge in (t["kToDense"], t["kToSerial"], t["ORCG_TAB_TO_DENSE"], t["ORCG_TAB_TO_SERIAL"]):
         assert any(a < edge <= b for a, b in zip(sizes, sizes[1:])), edge
     s = m.slices()
